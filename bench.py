@@ -30,11 +30,19 @@ step k+1 (one launch alone spends 17 % of its time in its first and last round,
 profiles/LOG.md C).  Every step still computes its whole batch; `--streams 1` runs
 them strictly one after the other.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the sweep kernel against the
-HBM roofline with ALGORITHMIC bytes (packed inputs + descriptors read, results +
-ops written; DESIGN.md section 4) over the HIP-event duration of the launch;
-`cpu_baseline` is the real reference (oracle/_ref, kind "reference") or the
-oracle restatement (kind "port") timed on the host cores, N=1 only.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps
+and prints the line (`value`, `ms_per_step`); `roofline` and `cpu_baseline` are
+null.  `--full` adds what the headline figure does not need: `roofline` prices
+the sweep kernel against the HBM roofline with ALGORITHMIC bytes (packed inputs
++ descriptors read, results + ops written) over the
+HIP-event duration of the launch; `cpu_baseline` is the real reference
+(oracle/_ref, kind "reference") or the oracle restatement (kind "port") timed on
+the host cores, N=1 only; and the checks of the results (buffer sets agree,
+rendered strings equal the host rendering, N > 1: what the gathers delivered).
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs): the same arguments give the same inputs, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -174,6 +182,41 @@ def cpu_baseline(mode, l1, l2, scoring, use_jump, sites, seed, target_s=15.0):
                 gcups_all_cores=multi, gcups_1core=single, host_cores_used=d["cores"])
 
 
+DUMP_RESULT_PAIRS = 1 << 19    # fixed-size results: of every pair up to this many, of a seeded sample of this many beyond
+DUMP_STRING_BYTES = 32 << 20   # CIGARs and rendered strings together: a seeded sample of at most 1024 pairs within this many bytes
+
+
+def dump_outputs(out_dir, res, pairs, slot, tb, ops, r1, r2, tri_sum):
+    """What the last timed step computed, as a caller of the path receives it, as out_dir/<name>.npy (at most 64 MB in all):
+    score, end_i, end_j, state and, with tracebacks, cigar_len per pair in float64 (exact for int32), of every pair or, beyond
+    DUMP_RESULT_PAIRS pairs, of a fixed seeded sample of them (result_pairs: their indices); with tracebacks the CIGAR op codes
+    (cigar_ops) and, when rendered, the two gapped strings (r1, r2) of a fixed seeded sample of pairs (string_pairs), float32
+    byte values in [sample, slot] rows, -1 past each pair's CIGAR length; C5full: triangle_score_sum, the sum of the scores of
+    the whole triangle."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(out_dir, name + ".npy"), a)
+    rp = np.arange(pairs) if pairs <= DUMP_RESULT_PAIRS else np.sort(np.random.default_rng(1).choice(pairs, DUMP_RESULT_PAIRS, replace=False))
+    h = res[:, torch.from_numpy(rp).to(res.device)].cpu().numpy().astype(np.float64)
+    for k, name in enumerate(["score", "end_i", "end_j", "state", "cigar_len"][:5 if tb else 4]):
+        save(name, h[k])
+    save("result_pairs", rp.astype(np.float64))
+    if tb:
+        ns = max(1, min(pairs, 1024, DUMP_STRING_BYTES // (3 * 4 * slot)))
+        sp = np.sort(np.random.default_rng(2).choice(pairs, ns, replace=False))
+        idx = torch.from_numpy(sp).to(res.device)
+        past = np.arange(slot)[None, :] >= res[4, idx].cpu().numpy()[:, None]
+        for name, buf in (("cigar_ops", ops), ("r1", r1), ("r2", r2)):
+            if buf is not None:
+                rows = buf[:pairs * slot].view(pairs, slot)[idx].cpu().numpy().astype(np.float32)
+                rows[past] = -1
+                save(name, rows)
+        save("string_pairs", sp.astype(np.float64))
+    if tri_sum is not None:
+        save("triangle_score_sum", np.array([float(tri_sum.item())]))
+
+
 def launch_ranks(n, backend):
     """Start `python -m torch.distributed.run --nnodes=1 --nproc-per-node n ... bench.py <same arguments>` as a child process (never
     an exec), pass its stderr through, relay the one JSON line rank 0 prints, return its exit code."""
@@ -235,7 +278,14 @@ def main():
     ap.add_argument("--no-render", action="store_true",
                     help="stop at the op codes (CIGARs): do not also turn them into the reference's two gapped strings on the GPU "
                          "inside every step (at_render_batch_device)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the roofline (per-step "
+                         "kernel times, one launch alone, the committed counters) and the checks of the results")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0's shard; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -257,7 +307,7 @@ def main():
 
     # CPU baseline first (child process, before this process touches the GPU)
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base = cpu_baseline(mode, l1, l2, scoring, use_jump, sites, seed)
 
     import numpy as np
@@ -339,7 +389,7 @@ def main():
         words, woff1, woff2, len1, len2, bits = A.pack_pairs(plist, bits=args.bits)
         d_words = torch.from_numpy(words.view(np.int32)).to(dev)
         d_woff1, d_woff2, d_len1, d_len2 = (torch.from_numpy(x).to(dev) for x in (woff1, woff2, len1, len2))
-        sample_rows = {k: plist[k] for k in range(0, pairs, max(1, pairs // 64))}
+        sample_rows = {k: plist[k] for k in range(0, pairs, max(1, pairs // 64))} if args.full else {}   # (the render check's sample)
     else:
         # generated and packed where it is used, in HBM (aligntools/c_amd/synth.py: the torch forms are bit-identical to the numpy
         # generators, tests/test_synth.py): 10 M pairs take seconds here and a quarter of an hour in numpy
@@ -347,7 +397,7 @@ def main():
         w1, w2 = (l1 + 15) // 16 + 1, (l2 + 15) // 16 + 1
         d_words = torch.zeros(pairs * (w1 + w2) + 4, dtype=torch.int32, device=dev)
         wv = d_words[:pairs * (w1 + w2)].view(pairs, w1 + w2)
-        sample_rows, want = {}, set(range(0, pairs, max(1, pairs // 64)))
+        sample_rows, want = {}, set(range(0, pairs, max(1, pairs // 64))) if args.full else set()   # (the render check's sample)
         for lo in range(0, pairs, 500000):
             nn = min(500000, pairs - lo)
             c = workload_codes_torch(mode, use_jump, seed, nn, l1, l2, rank * pairs + lo, dev)   # (C4: every other read is a mutated window of its contig)
@@ -545,7 +595,7 @@ def main():
     if gath:   # (the timed run starts with every buffer set free)
         for works in busy:
             del works[:]
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if args.full else None
     t0 = time.perf_counter()
     t_issued = run(args.steps, evs)
     sync_all()
@@ -555,33 +605,13 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
 
-    # ---- checks + accounting (outside the timed region) ----
-    kern_ms = sorted(a.elapsed_time(b) for a, b in evs)
-    kern_avg_ms = sum(kern_ms) / len(kern_ms)
-    # the same launch with nothing else in flight (what a rocprofv3 trace of `--streams 1` shows)
-    iso = []
-    for k in range(0 if full_triangle else 4):   # (a step of C5full is the whole triangle, minutes long: its timed steps were alone already)
-        ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ea.record()
-        step(args.steps - 1)   # the last step again, into the same buffers
-        eb.record()
-        torch.cuda.synchronize()
-        iso.append(ea.elapsed_time(eb))
-    kern_iso_ms = min(iso) if iso else kern_ms[0]
-    # every step of the timed run holds the results of the same batch
     last = args.steps - 1
-    if not allpairs and args.steps > 0:   # (all-vs-all sweeps a different slice of the triangle every step)
-        for k in range(max(0, last - (G if use_dist else NB) + 1), last):
-            assert torch.equal(res_of(k), res_of(last)), "buffer sets disagree"
-    d_ops = ops_of(last)
-    scores = res_of(last)[0].cpu().numpy()
-    nops = res_of(last)[4].cpu().numpy() if tb else np.zeros(pairs, dtype=np.int32)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res_of(last), pairs, l1 + l2, tb, ops_of(last) if tb else None,
+                     d_r1s[last % S], d_r2s[last % S], tri_sum[last % NB] if full_triangle else None)
     gather_info = None
-    if gath and args.steps > 0:
-        # what arrived: every rank's block of the last group, and in it this rank's own results
+    if gath:
         gb, row, rows = grp_of[last] % NGB, row_of[last], row_of[last] + 1
-        gnp = gathered[gb].cpu().numpy()
-        assert (gnp[rank, :rows] == grp_res[gb][:rows].cpu().numpy()).all(), "fixed-size gather: own block differs"
         try:
             bver = ".".join(str(x) for x in torch.cuda.nccl.version()) if args.backend == "nccl" else None
         except Exception:
@@ -589,39 +619,84 @@ def main():
         gather_info = {"world": world, "backend": "nccl (RCCL %s)" % bver if args.backend == "nccl" else "gloo (rehearsal: ranks may share a card)",
                        "ranks": ranks_info, "steps_per_collective": G, "fixed_bytes_per_rank_and_step": 20 * pairs}
         if cig:
-            # every rank's total per step is the sum of its gathered nops, and this rank's part of the payload is its own ops
-            # slots back to back
-            tots = h_tot[gb].numpy()
-            assert (gnp[:, :rows, 4, :].clip(min=0).sum(axis=2) == tots[:, :rows]).all(), "CIGAR gather: sizes disagree with the gathered nops"
-            pad = pay_pad[gb]
-            at = int(tots[rank, :row].sum())       # the group's payload is in (step, pair) order: the last step's CIGARs start here
-            mine = allpay[gb][:world * pad].view(world, pad)[rank, at:at + int(tots[rank, row])].cpu().numpy()
-            slots = d_ops[:pairs * (l1 + l2)].cpu().numpy().reshape(pairs, l1 + l2)
-            assert (mine == slots[np.arange(l1 + l2)[None, :] < nops[:, None]]).all(), "CIGAR gather: payload differs from the ops slots"
-            gather_info.update({"cigar_bytes_per_rank_and_step": int(tots[rank, row]), "cigar_group_payload_padded_to": int(pad),
+            tots = h_tot[gb].numpy()   # (on the host since the last payload_group)
+            gather_info.update({"cigar_bytes_per_rank_and_step": int(tots[rank, row]), "cigar_group_payload_padded_to": int(pay_pad[gb]),
                                 "phases": "per group of %d steps: one all_gather of the fixed-size results (sizes), then one padded "
                                           "payload; both on a communication stream, the payload of group g beside the sweeps of group g + 1" % G})
-    assert (scores > -(1 << 30)).all() and (nops >= 0).all(), "kernel reported a domain error"
-    if rend and args.steps > 0:
-        # the GPU-rendered strings of a sample equal what at_render (host, one pair) makes of the same ops
-        h_r1 = d_r1s[last % S].cpu().numpy().tobytes()
-        h_r2 = d_r2s[last % S].cpu().numpy().tobytes()
-        h_ops = d_ops[:slot_bytes].cpu().numpy()
-        h_res = res_of(last).cpu().numpy()
-        for k in sorted(sample_rows):
-            oo, nk = int(ops_off[k]), int(nops[k])
-            a, b = al.render(h_ops[oo:oo + nk].tobytes(), sample_rows[k][0], int(h_res[1][k]), sample_rows[k][1], int(h_res[2][k]))
-            assert a.encode("latin1") == h_r1[oo:oo + nk] and b.encode("latin1") == h_r2[oo:oo + nk], "rendered strings differ"
+
+    roofline = None
+    if args.full:
+        # ---- checks + accounting (outside the timed region) ----
+        kern_ms = sorted(a.elapsed_time(b) for a, b in evs)
+        kern_avg_ms = sum(kern_ms) / len(kern_ms)
+        # the same launch with nothing else in flight (what a rocprofv3 trace of `--streams 1` shows)
+        iso = []
+        for k in range(0 if full_triangle else 4):   # (a step of C5full is the whole triangle, minutes long: its timed steps were alone already)
+            ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ea.record()
+            step(last)   # the last step again, into the same buffers
+            eb.record()
+            torch.cuda.synchronize()
+            iso.append(ea.elapsed_time(eb))
+        kern_iso_ms = min(iso) if iso else kern_ms[0]
+        # every step of the timed run holds the results of the same batch
+        if not allpairs:   # (all-vs-all sweeps a different slice of the triangle every step)
+            for k in range(max(0, last - (G if use_dist else NB) + 1), last):
+                assert torch.equal(res_of(k), res_of(last)), "buffer sets disagree"
+        d_ops = ops_of(last)
+        scores = res_of(last)[0].cpu().numpy()
+        nops = res_of(last)[4].cpu().numpy() if tb else np.zeros(pairs, dtype=np.int32)
+        if gath:
+            # what arrived: every rank's block of the last group, and in it this rank's own results
+            gnp = gathered[gb].cpu().numpy()
+            assert (gnp[rank, :rows] == grp_res[gb][:rows].cpu().numpy()).all(), "fixed-size gather: own block differs"
+            if cig:
+                # every rank's total per step is the sum of its gathered nops, and this rank's part of the payload is its own ops
+                # slots back to back
+                assert (gnp[:, :rows, 4, :].clip(min=0).sum(axis=2) == tots[:, :rows]).all(), "CIGAR gather: sizes disagree with the gathered nops"
+                pad = pay_pad[gb]
+                at = int(tots[rank, :row].sum())       # the group's payload is in (step, pair) order: the last step's CIGARs start here
+                mine = allpay[gb][:world * pad].view(world, pad)[rank, at:at + int(tots[rank, row])].cpu().numpy()
+                slots = d_ops[:pairs * (l1 + l2)].cpu().numpy().reshape(pairs, l1 + l2)
+                assert (mine == slots[np.arange(l1 + l2)[None, :] < nops[:, None]]).all(), "CIGAR gather: payload differs from the ops slots"
+        assert (scores > -(1 << 30)).all() and (nops >= 0).all(), "kernel reported a domain error"
+        if rend:
+            # the GPU-rendered strings of a sample equal what at_render (host, one pair) makes of the same ops
+            h_r1 = d_r1s[last % S].cpu().numpy().tobytes()
+            h_r2 = d_r2s[last % S].cpu().numpy().tobytes()
+            h_ops = d_ops[:slot_bytes].cpu().numpy()
+            h_res = res_of(last).cpu().numpy()
+            for k in sorted(sample_rows):
+                oo, nk = int(ops_off[k]), int(nops[k])
+                a, b = al.render(h_ops[oo:oo + nk].tobytes(), sample_rows[k][0], int(h_res[1][k]), sample_rows[k][1], int(h_res[2][k]))
+                assert a.encode("latin1") == h_r1[oo:oo + nk] and b.encode("latin1") == h_r2[oo:oo + nk], "rendered strings differ"
     cells_per_step = float(pairs) * l1 * l2 * world
     if full_triangle:
         cells_per_step = float(nreads * (nreads - 1) // 2) * l1 * l2     # the whole triangle, whatever the number of ranks (strong scaling)
     gcups = cells_per_step * args.steps / elapsed / 1e9
-    # algorithmic HBM bytes of one launch on one GPU
-    bytes_in = words_nbytes + pairs * (8 + 8 + 4 + 4) + (pairs * 8 if tb else 0)
-    bytes_out = pairs * 16 + (pairs * 4 + int(nops.sum()) if tb else 0)
-    step_s = elapsed / max(1, args.steps)            # (launches overlap: a launch's own first-to-last-wave time is not a per-step figure)
-    achieved = (bytes_in + bytes_out) / step_s / 1e9
-    valu, traffic = valu_roofline(args.workload, pairs, tb, al.last_config, args.steps, elapsed, float(l1) * l2, A.kernel_source_sha16())
+    if args.full:
+        # algorithmic HBM bytes of one launch on one GPU
+        bytes_in = words_nbytes + pairs * (8 + 8 + 4 + 4) + (pairs * 8 if tb else 0)
+        bytes_out = pairs * 16 + (pairs * 4 + int(nops.sum()) if tb else 0)
+        step_s = elapsed / max(1, args.steps)            # (launches overlap: a launch's own first-to-last-wave time is not a per-step figure)
+        achieved = (bytes_in + bytes_out) / step_s / 1e9
+        valu, traffic = valu_roofline(args.workload, pairs, tb, al.last_config, args.steps, elapsed, float(l1) * l2, A.kernel_source_sha16())
+        roofline = dict(valu or {"bound": "valu", "achieved": None, "peak": None, "unit": "G wave-instr/s", "frac": None,
+                                 "note": "no SQ_INSTS_VALU profile for this kernel configuration under profiles/%s" % PROFILE_ROUND},
+                        traffic=traffic,
+                        kernel=("at_sweep16" if "packed16" in al.last_config else "at_myers" if "myers" in al.last_config else "at_sweep") + "<%s>" % mode +
+                               (" + at_walk16" if "walk kernel" in al.last_config else ""),
+                        kernel_avg_ms=kern_avg_ms, kernel_min_ms=kern_ms[0], kernel_alone_ms=kern_iso_ms, launches_in_flight=S,
+                        host_issue_ms_per_step=(t_issued - t0) * 1e3 / max(1, args.steps),
+                        gcups_one_launch_at_a_time=cells_per_step / world / (kern_iso_ms * 1e-3) / 1e9,
+                        # the HBM view BASELINE.json asks for, both ways: the ALGORITHMIC bytes of a launch over the time per step, and the
+                        # bytes the chip really moved (PMC FETCH_SIZE x 2 + WRITE_SIZE of the same kernel configuration) over it
+                        hbm={"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "achieved_counter": (traffic / step_s / 1e9) if traffic else None,
+                             "frac_counter": (traffic / step_s / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                             "algorithmic_bytes_per_launch": bytes_in + bytes_out,
+                             "counter_bytes_per_launch": traffic,
+                             "traffic_over_algorithmic": (traffic / float(bytes_in + bytes_out)) if traffic else None})
 
     if rank == 0:
         out = {
@@ -639,22 +714,7 @@ def main():
                        "pairs_per_gpu": pairs, "l1": l1, "l2": l2, "bits_per_base": bits, "kernel_config": al.last_config,
                        "streams": S,
                        "parallelism": "pairs sharded over %d GPU(s), one process per GPU" % world},
-            "roofline": dict(valu or {"bound": "valu", "achieved": None, "peak": None, "unit": "G wave-instr/s", "frac": None,
-                                      "note": "no SQ_INSTS_VALU profile for this kernel configuration under profiles/%s" % PROFILE_ROUND},
-                             traffic=traffic,
-                             kernel=("at_sweep16" if "packed16" in al.last_config else "at_myers" if "myers" in al.last_config else "at_sweep") + "<%s>" % mode +
-                                    (" + at_walk16" if "walk kernel" in al.last_config else ""),
-                             kernel_avg_ms=kern_avg_ms, kernel_min_ms=kern_ms[0], kernel_alone_ms=kern_iso_ms, launches_in_flight=S,
-                             host_issue_ms_per_step=(t_issued - t0) * 1e3 / max(1, args.steps),
-                             gcups_one_launch_at_a_time=cells_per_step / world / (kern_iso_ms * 1e-3) / 1e9,
-                             # the HBM view BASELINE.json asks for, both ways: the ALGORITHMIC bytes of a launch over the time per step, and the
-                             # bytes the chip really moved (PMC FETCH_SIZE x 2 + WRITE_SIZE of the same kernel configuration) over it
-                             hbm={"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                                  "achieved_counter": (traffic / step_s / 1e9) if traffic else None,
-                                  "frac_counter": (traffic / step_s / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                                  "algorithmic_bytes_per_launch": bytes_in + bytes_out,
-                                  "counter_bytes_per_launch": traffic,
-                                  "traffic_over_algorithmic": (traffic / float(bytes_in + bytes_out)) if traffic else None}),
+            "roofline": roofline,
             "cpu_baseline": base,
         }
         if gather_info:

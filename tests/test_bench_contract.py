@@ -16,7 +16,7 @@ KEYS = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
 def test_bench_prints_one_json_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-                        "--pairs", "30000", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
+                        "--pairs", "30000", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [x for x in p.stdout.splitlines() if x.strip()]
     assert len(lines) == 1, p.stdout
@@ -37,6 +37,41 @@ def test_bench_prints_one_json_line():
     hb = r["hbm"]
     assert hb["unit"] == "GB/s" and hb["peak"] == 8000.0 and abs(hb["frac"] - hb["achieved"] / hb["peak"]) < 1e-12
     assert d["value"] > 100 and abs(d["ms_per_step"] * d["value"] - 30000 * 150 * 150 / 1e6) < 1e-3 * d["ms_per_step"] * d["value"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_steps_and_dumps_the_last_ones_results(tmp_path):
+    """A plain run (no --full) prints the headline figure without the CPU baseline or the roofline, and --dump-outputs writes
+    what the last timed step computed: the same arrays from run to run, and the sampled pairs' scores and gapped strings are
+    the oracle's."""
+    import numpy as np
+    import oracle as O
+    from aligntools.c_amd.synth import workload_blob
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("out%d" % k)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                            "--pairs", "30000", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [x for x in p.stdout.splitlines() if x.strip()]
+        assert len(lines) == 1, p.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["roofline"] is None and d["cpu_baseline"] is None
+        assert d["value"] > 100 and abs(d["ms_per_step"] * d["value"] - 30000 * 150 * 150 / 1e6) < 1e-3 * d["ms_per_step"] * d["value"]
+        dumps.append({f[:-4]: np.load(out / f) for f in os.listdir(out)})
+    a, b = dumps
+    assert sorted(a) == ["cigar_len", "cigar_ops", "end_i", "end_j", "r1", "r2", "result_pairs", "score", "state", "string_pairs"]
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert len(a["score"]) == 30000 and (a["result_pairs"] == np.arange(30000)).all()
+    blob = workload_blob("local", False, 0x5EED0002, 30000, 150, 150)
+    for i, k in enumerate(a["string_pairs"].astype(np.int64)[:64]):
+        r = O.align(O.LOCAL, blob[k, :150].tobytes(), blob[k, 150:].tobytes(), 2, -2, -5, -2)
+        n = int(a["cigar_len"][k])
+        assert a["score"][k] == r["score"] and n == len(r["r1"]), k
+        assert bytes(a["r1"][i, :n].astype(np.uint8)) == r["r1"].encode() and bytes(a["r2"][i, :n].astype(np.uint8)) == r["r2"].encode(), k
+        assert (a["r1"][i, n:] == -1).all() and (a["cigar_ops"][i, n:] == -1).all() and (a["cigar_ops"][i, :n] >= 0).all(), k
 
 
 def test_bench_gpus_n_starts_its_own_launcher():
@@ -87,7 +122,7 @@ def test_bench_under_the_launcher_gathers_groups_of_steps(world, backend, extra)
     port = 29810 + world
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--pairs", "20000", "--no-cpu-baseline",
-                        "--backend", backend] + extra, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--backend", backend, "--full"] + extra, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.strip().startswith("{")]
     assert len(lines) == 1, p.stdout

@@ -1,4 +1,4 @@
-"""Condense a bench.py JSON line (stdin) to: label, GCUPS, kernel avg/min ms, kernel config."""
+"""Condense a `bench.py --full` JSON line (stdin) to: label, GCUPS, kernel avg/min ms, kernel config."""
 import json
 import sys
 

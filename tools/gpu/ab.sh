@@ -11,6 +11,6 @@ for W in $WLS; do for V in $VARS; do
   NAME=${V%%=*}; SPEC=${V#*=}
   ENVS=""
   if [ "${SPEC#@}" != "$SPEC" ]; then ENVS="AT_LIB_PATH=${SPEC#@}"; elif [ -n "$SPEC" ]; then ENVS=$(echo "$SPEC" | tr ',' ' '); fi
-  env $ENVS timeout -k 10 400 python3 bench.py --workload $W --no-cpu-baseline "$@" 2>> $O/ab.err | python3 -c "
+  env $ENVS timeout -k 10 400 python3 bench.py --workload $W --no-cpu-baseline --full "$@" 2>> $O/ab.err | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); r={'variant':'$NAME','workload':'$W','gcups':round(d['value'],1),'ms_per_step':round(d['ms_per_step'],4),'alone_gcups':round(d['roofline']['gcups_one_launch_at_a_time'],1),'kernel_config':d['config']['kernel_config']}; print(json.dumps(r))" | tee -a $O/ab.jsonl | cut -c1-200
 done; done

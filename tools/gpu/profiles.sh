@@ -23,15 +23,15 @@ cp $O/valu_issue.json profiles/$RD/valu_issue.json
 cp $O/traffic_*.json profiles/$RD/
 : > $O/workloads_bench.jsonl
 for W in C2 C3 C4 C5 C5all E1k E150; do
-  timeout -k 10 400 python3 bench.py --workload $W --steps 60 >> $O/workloads_bench.jsonl 2>> $O/bench.err
+  timeout -k 10 400 python3 bench.py --workload $W --steps 60 --full >> $O/workloads_bench.jsonl 2>> $O/bench.err
   echo "bench $W done"
 done
 for W in C2 C3 C4; do
-  timeout -k 10 300 python3 bench.py --workload $W --steps 60 --no-traceback --no-cpu-baseline >> $O/workloads_bench.jsonl 2>> $O/bench.err
+  timeout -k 10 300 python3 bench.py --workload $W --steps 60 --no-traceback --no-cpu-baseline --full >> $O/workloads_bench.jsonl 2>> $O/bench.err
 done
-timeout -k 10 300 python3 bench.py --workload C5all --steps 60 --no-cpu-baseline --min-score 30 >> $O/workloads_bench.jsonl 2>> $O/bench.err
+timeout -k 10 300 python3 bench.py --workload C5all --steps 60 --no-cpu-baseline --min-score 30 --full >> $O/workloads_bench.jsonl 2>> $O/bench.err
 timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/c2_driver_style_bench.json 2>> $O/bench.err
-timeout -k 10 300 python3 bench.py --streams 1 --steps 60 --no-cpu-baseline > $O/c2_streams1_bench.json 2>> $O/bench.err
+timeout -k 10 300 python3 bench.py --streams 1 --steps 60 --no-cpu-baseline --full > $O/c2_streams1_bench.json 2>> $O/bench.err
 fi
 if [ $PART != main ]; then
 # two-pass tracebacks against the one-pass kernels, same box: launches in flight (3, 4) and one launch at a time.  AT_TWO_PASS: 0 never,
@@ -62,6 +62,6 @@ timeout -k 10 600 python3 tools/ragged_rate.py > $O/ragged_rate.txt 2>&1 || true
 timeout -k 10 120 python3 tools/pcie_rate.py > $O/pcie_rate.txt 2>&1 || true
 timeout -k 10 300 python3 tools/cli_latency.py > $O/cli_latency.txt 2>&1 || true
 echo "host rates done"
-timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/dist_nccl1.json 2> $O/dist_nccl1.err || true
-timeout -k 10 300 python3 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --backend gloo --workload C4 --pairs 20000 > $O/dist_gloo2_C4_self_launched.json 2> $O/dist_gloo2_C4.err || true
+timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --full > $O/dist_nccl1.json 2> $O/dist_nccl1.err || true
+timeout -k 10 300 python3 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --full --backend gloo --workload C4 --pairs 20000 > $O/dist_gloo2_C4_self_launched.json 2> $O/dist_gloo2_C4.err || true
 echo "rehearsals done"; du -sh $O | tail -1

@@ -14,9 +14,9 @@ timeout -k 10 1100 python3 -m pytest tests -q -m gpu --durations=8 > $O/pytest_g
 tail -12 $O/pytest_gpu_final.log
 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 && tail -1 $O/smoke.log
 : > $O/full_size_bench.jsonl
-timeout -k 10 600 python3 bench.py --workload C4full --steps 5 --warmup 1 >> $O/full_size_bench.jsonl 2>> $O/bench.err
-timeout -k 10 900 python3 bench.py --workload C5full --steps 1 --warmup 0 --streams 1 >> $O/full_size_bench.jsonl 2>> $O/bench.err
-timeout -k 10 400 python3 bench.py --workload C5full --steps 1 --warmup 0 --streams 1 --no-cpu-baseline --min-score 30 >> $O/full_size_bench.jsonl 2>> $O/bench.err
+timeout -k 10 600 python3 bench.py --workload C4full --steps 5 --warmup 1 --full >> $O/full_size_bench.jsonl 2>> $O/bench.err
+timeout -k 10 900 python3 bench.py --workload C5full --steps 1 --warmup 0 --streams 1 --full >> $O/full_size_bench.jsonl 2>> $O/bench.err
+timeout -k 10 400 python3 bench.py --workload C5full --steps 1 --warmup 0 --streams 1 --no-cpu-baseline --min-score 30 --full >> $O/full_size_bench.jsonl 2>> $O/bench.err
 cut -c1-300 $O/full_size_bench.jsonl
 fi
 [ $PART = tests ] && exit 0
