@@ -109,7 +109,11 @@ int dev_buf(at_handle *h, Comm *c, size_t need)
 	if (need <= c->d_bytes) return AT_OK;
 	if (c->d_buf) (void)hipFree(c->d_buf);
 	c->d_buf = nullptr; c->d_bytes = 0;
-	if (hipMalloc(&c->d_buf, need + 4096) != hipSuccess) return at_comm_fail(h, AT_ERR_NOMEM, "at_comm: hipMalloc of the staging buffer failed");
+	if (hipMalloc(&c->d_buf, need + 4096) != hipSuccess) {
+		c->d_buf = nullptr;
+		(void)hipGetLastError();   /* (the failure would stay the thread's last error: at_hip.hip, grow) */
+		return at_comm_fail(h, AT_ERR_NOMEM, "at_comm: hipMalloc of the staging buffer failed");
+	}
 	c->d_bytes = need + 4096;
 	return AT_OK;
 }

@@ -23,6 +23,10 @@
 #include <thread>
 #include <vector>
 
+#ifndef AT_DIAG_SWEEP_ONLY
+#define AT_DIAG_SWEEP_ONLY 0   /* 1: a throw-away build in which AT_DIAG_NO_WALK_KERNEL=1 skips pass 2 (tools/gpu/profiles.sh, through tools/ab_lib.sh) */
+#endif
+
 using at::SweepArgs;
 using at::Sweep16Args;
 
@@ -90,7 +94,9 @@ struct at_handle {
 	uint32_t *d_sitemask = nullptr; size_t sitemask_words = 0; int sitemask_for_l2 = -1; bool sitemask_dirty = true;
 	uint32_t *d_ws = nullptr; size_t ws_bytes = 0;
 	uint32_t *d_ck = nullptr; size_t ck_bytes = 0;   /* two-pass tracebacks with a walk kernel: a launch's checkpoints */
-	bool ck_alloc_failed = false;                    /* ... could not be allocated once: this handle keeps to the rounds inside the sweep's kernel */
+	bool ck_alloc_failed = false;                    /* ... could not be allocated once: this handle keeps to the rounds inside the sweep's kernel
+	                                                  * for the rest of its life (a later batch would only meet the same shortage) */
+	bool ck_skip = false;                            /* this call only: one work item's checkpoints exceed AT_CK_CAP_MB */
 	unsigned long long *d_queue = nullptr;
 	int last_span = 0;              /* max_len1 + max_len2 of the handle's latest batch: the rendering kernel's hint for its group width */
 	void *d_in = nullptr; size_t in_bytes = 0;
@@ -115,7 +121,8 @@ struct at_handle {
 	HostPool *pool = nullptr;       /* ... and the threads they run on */
 	void *comm = nullptr;           /* multi-process batches: the communicator (at_comm.hip) */
 	char err[512] = {0};
-	char cfg[320] = "none";
+	char cfg[640] = "none";
+	int last_render_lanes = 0;      /* lanes per pair of the latest at_render_batch_device (at_last_config of the host entry's strings) */
 };
 
 static thread_local char g_err[512] = "no error";   /* per thread: the host entry runs chunks on helper threads */
@@ -142,12 +149,20 @@ static int guarded(at_handle *h, const char *who, F &&body)
 	catch (...) { return fail(h, AT_ERR_NOMEM, "%s: unknown C++ exception", who); }
 }
 
+/* (a failed call's error is also the thread's last error: read away, so that the failure is reported once, by our return code) */
 #define HIP_TRY(h, call)                                                                      \
 	do {                                                                                      \
 		hipError_t e_ = (call);                                                               \
-		if (e_ != hipSuccess)                                                                 \
+		if (e_ != hipSuccess) {                                                               \
+			(void)hipGetLastError();                                                          \
 			return fail((h), AT_ERR_NODEVICE, "%s: %s", #call, hipGetErrorString(e_));        \
+		}                                                                                     \
 	} while (0)
+
+/* The runtime keeps a failed call's error as the thread's last error until somebody reads it, and the check behind a launch
+ * (HIP_TRY(h, hipGetLastError())) would report such a leftover -- of an earlier call, ours or the caller's -- as the launch's own:
+ * every entry that launches reads it away first */
+static inline void drop_stale_error() { (void)hipGetLastError(); }
 
 extern "C" const char *at_last_error(const at_handle *h) { return h ? h->err : g_err; }
 extern "C" const char *at_last_config(const at_handle *h) { return h ? h->cfg : "none"; }
@@ -580,13 +595,26 @@ static bool packed16_kernel_exists(int kmode, const Layout16 &P, bool tb, int ts
 	return (rag ? at_pick16_rag(kmode, P.g, P.k, st, tb, bits) : at_pick16(kmode, P.g, P.k, ts, st, tb, bits)) != nullptr;
 }
 
-static int grow(at_handle *h, void **p, size_t *have, size_t need)
+/* AT_DIAG_FAIL_ALLOC=ck / ws: that buffer's next hipMalloc asks for 2^50 bytes, so the runtime itself refuses (tests of the fallbacks
+ * and of the error state a failed allocation leaves; no device memory is held) */
+static bool diag_fail_alloc(const char *which)
+{
+	const char *v = getenv("AT_DIAG_FAIL_ALLOC");
+	return which && v && strcmp(v, which) == 0;
+}
+
+static int grow(at_handle *h, void **p, size_t *have, size_t need, const char *which = nullptr)
 {
 	if (need <= *have) return AT_OK;
 	if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
 	need = need + need / 8 + 4096;
+	if (diag_fail_alloc(which)) need = (size_t)1 << 50;
 	hipError_t e = hipMalloc(p, need);
-	if (e != hipSuccess) return fail(h, AT_ERR_NOMEM, "hipMalloc(%zu): %s", need, hipGetErrorString(e));
+	if (e != hipSuccess) {
+		*p = nullptr;
+		(void)hipGetLastError();   /* the runtime keeps the failure as the thread's last error: the next launch check (ours or the caller's) would report it */
+		return fail(h, AT_ERR_NOMEM, "hipMalloc(%zu): %s", need, hipGetErrorString(e));
+	}
 	*have = need;
 	return AT_OK;
 }
@@ -598,7 +626,11 @@ static int grow_pinned(at_handle *h, void **p, size_t *have, size_t need)
 	if (*p) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
 	need = need + need / 4 + 4096;
 	hipError_t e = hipHostMalloc(p, need, hipHostMallocDefault);
-	if (e != hipSuccess) return fail(h, AT_ERR_NOMEM, "hipHostMalloc(%zu): %s", need, hipGetErrorString(e));
+	if (e != hipSuccess) {
+		*p = nullptr;
+		(void)hipGetLastError();   /* (as in grow) */
+		return fail(h, AT_ERR_NOMEM, "hipHostMalloc(%zu): %s", need, hipGetErrorString(e));
+	}
 	*have = need;
 	return AT_OK;
 }
@@ -693,7 +725,7 @@ static int plan_launch(at_handle *h, const char *tag, int k, long long nwork, lo
 		if (slot_words * 4 > cap) return fail(h, AT_ERR_NOMEM, "one pair needs %lld workspace bytes (cap %lld)", slot_words * 4, cap);
 		grid = std::max(1LL, std::min(grid, cap / (slot_words * 4)));
 		void *p = h->d_ws; size_t have = h->ws_bytes;
-		int rc = grow(h, &p, &have, (size_t)(grid * slot_words * 4));
+		int rc = grow(h, &p, &have, (size_t)(grid * slot_words * 4), "ws");
 		h->d_ws = (uint32_t *)p; h->ws_bytes = have;
 		if (rc) return rc;
 		pl->ws = h->d_ws;
@@ -760,6 +792,7 @@ extern "C" int at_render_batch_device(at_handle *h, int64_t npairs,
 	if (!d_seq || !d_woff1 || !d_woff2 || !d_end_i || !d_end_j || !d_ops || !d_ops_off || !d_nops || !d_r1 || !d_r2)
 		return fail(h, AT_ERR_ARG, "NULL device pointer");
 	HIP_TRY(h, hipSetDevice(h->device));
+	drop_stale_error();
 	hipStream_t s = (hipStream_t)stream_;
 	at::RenderArgs ra;
 	ra.npairs = npairs; ra.seq = d_seq; ra.woff1 = (const long long *)d_woff1; ra.woff2 = (const long long *)d_woff2;
@@ -770,6 +803,7 @@ extern "C" int at_render_batch_device(at_handle *h, int64_t npairs,
 	const long long rw = env_ll("AT_RENDER_GROUP", h->last_span >= 1024 ? 64 : 16);
 	const int w = rw == 64 ? 64 : rw == 32 ? 32 : rw == 8 ? 8 : 16;
 	const int per_block = 4 * (64 / w);
+	h->last_render_lanes = w;
 	const unsigned grid = (unsigned)std::min<int64_t>((npairs + per_block - 1) / per_block, 16LL * h->ncu);
 #define AT_RENDER(B, W) hipLaunchKernelGGL((at::at_render_k<B, W>), dim3(grid), dim3(256), 0, s, ra)
 	if (bits == 2) { if (w == 64) AT_RENDER(2, 64); else if (w == 32) AT_RENDER(2, 32); else if (w == 8) AT_RENDER(2, 8); else AT_RENDER(2, 16); }
@@ -800,6 +834,7 @@ extern "C" int at_compact_ops_device(at_handle *h, int64_t npairs,
 	if (npairs < 0 || packed_cap < 0) return fail(h, AT_ERR_ARG, "negative size");
 	if (!d_ops || !d_ops_off || !d_nops || !d_packed || !d_packed_off) return fail(h, AT_ERR_ARG, "NULL device pointer");
 	HIP_TRY(h, hipSetDevice(h->device));
+	drop_stale_error();
 	hipStream_t s = (hipStream_t)stream_;
 	if (npairs == 0) {
 		HIP_TRY(h, hipMemsetAsync(d_packed_off, 0, 8, s));
@@ -835,6 +870,7 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 	if (tb && (!d_ops || !d_ops_off || !d_nops)) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
 	hipStream_t stream = (hipStream_t)stream_;
 	HIP_TRY(h, hipSetDevice(h->device));
+	drop_stale_error();
 
 	/* exact-int32 range: real scores stay within 2^24, sentinel at -2^26 (at_sweep.hip.h) */
 	long long maxabs = 0;
@@ -909,6 +945,7 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 	 * -28 %, profiles/r04/two_pass_ab.txt), AT_TWO_PASS=0: never (A/B runs) */
 	bool two_pass = false;
 	int tp_split = 0;   /* pass 2: 0 the rounds inside the sweep's kernel, 1 a walk kernel behind it */
+	const char *ck_note = "";
 	const long long tp_mode = env_ll("AT_TWO_PASS", 1);
 	if (ts && tb && !rag && kmode <= at::K_FITJ && tp_mode) {
 		Layout16 P2 = layout16_for(false, kmode == at::K_FITJ, max_len1, max_len2, ts, 0, false, kmode, 0, 1);
@@ -918,7 +955,12 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		 * second sequence (tp_split_narrow_default); AT_TP_SPLIT=1: wherever a walk kernel exists, 0: nowhere (the rounds inside the sweep's kernel) */
 		const bool narrow_default = P2.g == 8 && tp_split_narrow_default(kmode, max_len1, max_len2);
 		const bool split_default = P2.g == 64 || narrow_default;
-		const int split_req = env_ll("AT_TP_SPLIT", split_default ? 1 : 0) && !h->ck_alloc_failed && at_pick_walk16(kmode, P2.g, P2.k, ts, bits) ? 1 : 0;
+		const bool split_want = env_ll("AT_TP_SPLIT", split_default ? 1 : 0) && at_pick_walk16(kmode, P2.g, P2.k, ts, bits);
+		const int split_req = split_want && !h->ck_alloc_failed && !h->ck_skip ? 1 : 0;
+		/* (the fallback without a checkpoint buffer: the rounds inside the sweep's kernel on the 64-lane groups, the one-pass kernels on the
+		 * 8-lane groups -- at_last_config says so) */
+		if (split_want && !split_req) ck_note = h->ck_skip ? " [one work item's checkpoints exceed AT_CK_CAP_MB: no separate pass 2]"
+		                                                   : " [checkpoint buffer unavailable on this handle: no separate pass 2]";
 		if ((P2.g == 64 || tp_mode >= 2 || (split_req && narrow_default)) && (long long)P2.g * P2.k >= max_len1 && at_pick16_tp(kmode, P2.g, P2.k, ts, bits) &&
 		    choose_store(P2.off_ptr, 1, true) == 1) {
 			two_pass = true;
@@ -945,7 +987,16 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			brow_words = (tpm.brow_words + 63) & ~63LL;
 			const long long tail_reserve = tail_ok ? 16LL * h->ncu * tpt.words * 4 : 0;
 			const long long items = (cap - tail_reserve - brow_words * 4) / (tpm.words * 4 + 16LL * per_wave);
-			if (items < 1) return fail(h, AT_ERR_NOMEM, "two-pass tracebacks: one work item's checkpoints (%lld bytes) exceed AT_CK_CAP_MB", tpm.words * 4);
+			if (items < 1) {
+				/* not even one work item's checkpoints fit the cap: this batch without the walk kernel (nothing has been launched yet) */
+				struct SkipForThisCall {   /* (reset however the call below ends: an exception goes on to guarded()) */
+					at_handle *h;
+					explicit SkipForThisCall(at_handle *hh) : h(hh) { h->ck_skip = true; }
+					~SkipForThisCall() { h->ck_skip = false; }
+				} skip(h);
+				return align_device(h, mode, npairs, d_seq, bits, d_woff1, d_len1, d_woff2, d_len2, max_len1, max_len2, uniform_shape, want_traceback,
+				                    d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream_, ap_n, ap_first, d_order, rag, only_if, only_val);
+			}
 			piece = std::min<int64_t>(npairs, items * per_wave);
 			const long long forced = env_ll("AT_CK_PIECE_PAIRS", 0);   /* (tests: pieces of this many pairs, whatever the cap) */
 			if (forced > 0) piece = std::min<int64_t>(piece, std::max<long long>(1, forced / per_wave) * per_wave);
@@ -958,7 +1009,7 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			const int cb = at::ck_steps(L.g), nsm = kmode == at::K_FITJ ? L.nsm : 0;
 			return (size_t)((nsm + 1) / 2 * 2 + (L.k > 16 ? 0 : (cb + 1) * 128) + (ptr_in_lds ? 64 * walk_lane_words(L) : 0)) * 4;   /* (walk16_lds_words) */
 		};
-		std::string cfg_first;
+		std::string cfg_first, walk_last;   /* (at_last_config: the first piece's configuration, the last piece's walkers) */
 		for (int64_t first = 0; first < npairs; first += piece) {
 		const int64_t np = std::min<int64_t>(piece, npairs - first);
 		Sweep16Args b;
@@ -1007,7 +1058,10 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			/* AT_TP_RESERVE=n: the sweep leaves n wave slots per CU to the walk kernels of the launches around it (its waves are
 			 * persistent: a walk kernel queued behind it otherwise waits for the whole sweep of the NEXT launch to drain) */
 			const long long rsv = env_ll("AT_TP_RESERVE", 0) * h->ncu;
-			if (rsv > 0 && pl.grid > rsv && nwork > pl.grid - rsv) pl.grid = std::max<long long>(h->ncu, pl.grid - rsv);
+			if (rsv > 0 && pl.grid > rsv && nwork > pl.grid - rsv) {
+				pl.grid = std::max<long long>(h->ncu, pl.grid - rsv);
+				snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " (AT_TP_RESERVE: sweep grid=%lld)", pl.grid);
+			}
 		}
 		int64_t n_tail = 0;
 		if (tail_ok && nwork > pl.grid) {
@@ -1042,15 +1096,21 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			const long long end_words = ((np * 4) + 63) & ~63LL;
 			const size_t need = (size_t)(brow_words + end_words + n_main_items * tpm.words + n_tail_items * tpt.words) * 4;
 			void *pc = h->d_ck; size_t have = h->ck_bytes;
-			rc = grow(h, &pc, &have, need);
+			const std::string err_before = h->err, g_err_before = g_err;
+			rc = grow(h, &pc, &have, need, "ck");
 			h->d_ck = (uint32_t *)pc; h->ck_bytes = have;
 			if (rc && first == 0) {
 				/* no room for a launch's checkpoints (several handles on one card, a small AT_CK_CAP_MB would have cut the batch into pieces):
 				 * nothing has been launched yet -- the same batch with the rounds inside the sweep's kernel, whose checkpoints live in the
-				 * resident wavefronts' slots */
+				 * resident wavefronts' slots.  A fallback that works is no error: the hipMalloc text goes again */
 				h->ck_alloc_failed = true;
-				return align_device(h, mode, npairs, d_seq, bits, d_woff1, d_len1, d_woff2, d_len2, max_len1, max_len2, uniform_shape, want_traceback,
-				                    d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream_, ap_n, ap_first, d_order, rag, only_if, only_val);
+				rc = align_device(h, mode, npairs, d_seq, bits, d_woff1, d_len1, d_woff2, d_len2, max_len1, max_len2, uniform_shape, want_traceback,
+				                  d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream_, ap_n, ap_first, d_order, rag, only_if, only_val);
+				if (rc == AT_OK) {
+					snprintf(h->err, sizeof h->err, "%s", err_before.c_str());
+					snprintf(g_err, sizeof g_err, "%s", g_err_before.c_str());
+				}
+				return rc;
 			}
 			if (rc) return rc;
 			b.ck_brow = h->d_ck; bt.ck_brow = h->d_ck;
@@ -1064,7 +1124,8 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			HIP_TRY(h, hipFuncSetAttribute((const void *)fn16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.dyn_lds));
 		hipLaunchKernelGGL(fn16, dim3((unsigned)pl.grid), dim3(64), pl.dyn_lds, stream, b, bt);
 		HIP_TRY(h, hipGetLastError());
-		if (tp_split && !env_ll("AT_DIAG_NO_WALK_KERNEL", 0)) {   /* (1: throw-away runs without pass 2 -- what does the sweep alone reach?  Every pair reports garbage ops) */
+		if (tp_split && !(AT_DIAG_SWEEP_ONLY && env_ll("AT_DIAG_NO_WALK_KERNEL", 0))) {   /* (diagnostic builds, -DAT_DIAG_SWEEP_ONLY=1: AT_DIAG_NO_WALK_KERNEL=1
+			* -- throw-away runs without pass 2: what does the sweep alone reach?  Every pair reports garbage ops.  The product ignores the knob) */
 			/* the 64-lane groups: teams of lanes per pair of alignments (walk16_team_wave; AT_WALK_TEAMS=0: one walker per half-lane there too) */
 			const bool teams = env_ll("AT_WALK_TEAMS", P.g == 64 ? 1 : 0) && at_pick_walk16(kmode, P.g, P.k, ts, bits, 1);
 			at_walk16_fn wf = at_pick_walk16(kmode, P.g, P.k, ts, bits, teams);
@@ -1081,13 +1142,20 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			const int tpw = 64 / at_walk16_team_lanes(P.g);   /* teams per wavefront */
 			const long long wteams = ((nm + 1) / 2 + tpw - 1) / tpw;
 			hipLaunchKernelGGL(wf, dim3((unsigned)((teams ? wteams : wmain) + (n_tail + 127) / 128)), dim3(64), lds, stream, b, bt);
+			/* (the main alignments' walker wavefronts: with fewer than one per 128 alignments, they refill from the counters) */
+			char wnote[128];
+			snprintf(wnote, sizeof wnote, " [walkers: %lld wavefronts%s for %lld alignments]", teams ? wteams : wmain, teams ? " of teams" : "", (long long)nm);
+			snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), "%s", wnote);
+			walk_last = wnote;
 			HIP_TRY(h, hipGetLastError());
 		}
 		if (n_tail > 0)
 			snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " + last %lld pairs as 32-lane items (rows/lane=%d)", (long long)n_tail, PT.k);
 		if (first == 0) cfg_first = h->cfg;
 		}
-		if (piece < npairs) snprintf(h->cfg, sizeof h->cfg, "%.200s; in pieces of %lld pairs", cfg_first.c_str(), (long long)piece);
+		if (piece < npairs) snprintf(h->cfg, sizeof h->cfg, "%.360s; in pieces of %lld pairs%s%s", cfg_first.c_str(), (long long)piece,
+		                              walk_last.empty() ? "" : "; last piece", walk_last.c_str());
+		if (ck_note[0]) snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), "%s", ck_note);
 		return AT_OK;
 	}
 
@@ -1316,6 +1384,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	if (!tb) ops_lo = 0;
 	ops_total -= ops_lo;
 	HIP_TRY(h, hipSetDevice(h->device));
+	drop_stale_error();
 
 	/* ---- inputs go up RAW; packing happens on the GPU (at_pack.hip.h).  Host work is O(npairs): one pass writes every descriptor
 	 * ---- array into ONE page-locked block that mirrors the device block, so all of them travel in one copy; the raw bytes are
@@ -1382,6 +1451,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	/* pure-ACGT batches are packed HERE, while they are staged: the words go up (a quarter of the bytes), the raw blob and the GPU's
 	 * packing kernel are skipped.  The first byte that is not ACGT ends the attempt: the raw path below takes the whole chunk. */
 	bool host_packed = false;
+	int up_pieces = 0;                                 /* (at_last_config: how the bytes went up) */
 	if (!force8 && !caller_pinned && host_pack_available() && env_ll("AT_HOST_PACK", 1)) {
 		rc = grow_pinned(h, &h->hp_blob, &h->hp_blob_bytes, (size_t)(nwords2 + 4) * 4 + 64);
 		if (rc) return rc;
@@ -1397,10 +1467,11 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 				const int64_t upto = k + 1 == 2 * npairs ? nwords2 + 4 : done;
 				HIP_TRY(h, hipMemcpyAsync(d_words + sent, hw + sent, (size_t)(upto - sent) * 4, hipMemcpyHostToDevice, s));
 				sent = upto;
+				++up_pieces;
 			}
 		}
 		host_packed = ok;
-		if (!ok) HIP_TRY(h, hipStreamSynchronize(s));     /* (hp_blob is about to be reused for the raw bytes) */
+		if (!ok) { HIP_TRY(h, hipStreamSynchronize(s)); up_pieces = 0; }     /* (hp_blob is about to be reused for the raw bytes) */
 	}
 	if (host_packed) {
 	} else if (caller_pinned) HIP_TRY(h, hipMemcpyAsync(d_blob, up_src, (size_t)blob_bytes, hipMemcpyHostToDevice, s));
@@ -1412,6 +1483,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 			const size_t nb = std::min(piece, (size_t)blob_bytes - at);
 			memcpy((char *)h->hp_blob + at, up_src + at, nb);
 			HIP_TRY(h, hipMemcpyAsync(d_blob + at, (char *)h->hp_blob + at, nb, hipMemcpyHostToDevice, s));
+			++up_pieces;
 		}
 	}
 	at::PackArgs pa;
@@ -1618,6 +1690,13 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 		if (rc) return rc;
 	}
 	htrace("chunk: sweep queued, pair", pair_base);
+	{
+		char note[96];
+		if (host_packed) snprintf(note, sizeof note, " [upload: 2-bit words packed on the host, %d pieces]", up_pieces);
+		else if (caller_pinned) snprintf(note, sizeof note, " [upload: raw bytes from the caller's page-locked memory]");
+		else snprintf(note, sizeof note, " [upload: raw bytes staged, %d pieces]", up_pieces);
+		snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), "%s", note);
+	}
 	/* ---- results: the five fixed-size arrays come down in ONE copy into page-locked memory.  Only the bytes of each pair's own
 	 * ---- traceback travel and are written: the used part of every ops slot (or string slot) is packed back to back on the GPU and
 	 * ---- comes down with the same synchronisation -- as many bytes as the previous call's payload suggests, the rest (if this
@@ -1653,6 +1732,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 			rc = at_render_batch_device(h, npairs, d_words, bits, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_opsoff, d_nops,
 			                            d_pk1, d_pk2, d_stroff, 1, s);
 			if (rc) return rc;
+			snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " [strings: %d lanes per pair]", h->last_render_lanes);
 			HIP_TRY(h, hipMemcpyAsync(p_rflag, h->d_rflag, 4, hipMemcpyDeviceToHost, s));
 		}
 		HIP_TRY(h, hipMemcpyAsync(h_poff, d_poff, (size_t)(npairs + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -1795,6 +1875,7 @@ static int upload_reads(at_handle *h, int mode, int64_t nreads, const uint8_t *s
 		blob_bytes = std::max<int64_t>(blob_bytes, soff[(size_t)k] + len[k]);
 	}
 	HIP_TRY(h, hipSetDevice(h->device));
+	drop_stale_error();
 	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
 	const size_t b_words = al((size_t)(std::max(nwords2, nwords8) + 4) * 4), b_off = al((size_t)nreads * 8), b_len = al((size_t)nreads * 4);
 	const size_t b_blob = al((size_t)blob_bytes + 32);   /* (at_pack reads whole dwords: up to 20 bytes behind the last base) */
@@ -1857,8 +1938,11 @@ static int allpairs_scores(at_handle *h, int mode, int64_t nreads, const ReadSet
 	if (rc) return rc;
 	if (h->pin_bytes < 2 * 4 * b_res) {
 		if (h->h_pin) { (void)hipHostFree(h->h_pin); h->h_pin = nullptr; h->pin_bytes = 0; }
-		if (hipHostMalloc(&h->h_pin, 2 * 4 * b_res, hipHostMallocDefault) != hipSuccess)
+		if (hipHostMalloc(&h->h_pin, 2 * 4 * b_res, hipHostMallocDefault) != hipSuccess) {
+			h->h_pin = nullptr;
+			(void)hipGetLastError();   /* (as in grow) */
 			return fail(h, AT_ERR_NOMEM, "hipHostMalloc(%zu) for the result slices failed", 2 * 4 * b_res);
+		}
 		h->pin_bytes = 2 * 4 * b_res;
 	}
 	if (!h->copy_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));

@@ -36,10 +36,13 @@ fi
 if [ $PART != main ]; then
 # two-pass tracebacks against the one-pass kernels, same box: launches in flight (3, 4) and one launch at a time.  AT_TWO_PASS: 0 never,
 # 1 default routing -- the 64-lane groups x 16 rows --, 2 wherever a CK kernel exists; AT_TP_SPLIT=1: pass 2 as a kernel of its own
-# (at_walk16.hip.h); AT_DIAG_NO_WALK_KERNEL=1: the sweep with checkpoints alone (no pass 2: what a free pass 2 would reach)
+# (at_walk16.hip.h); AT_DIAG_NO_WALK_KERNEL=1: the sweep with checkpoints alone (no pass 2: what a free pass 2 would reach) -- honoured
+# only by a diagnostic build (-DAT_DIAG_SWEEP_ONLY=1, tools/ab_lib.sh), which that leg loads through AT_LIB_PATH
+bash tools/ab_lib.sh sweeponly "-DAT_DIAG_SWEEP_ONLY=1" > /dev/null
 : > $O/two_pass_ab.jsonl
 for W in C2 C3 C4; do for V in "0 0 0" "1 0 0" "2 0 0" "2 1 0" "2 1 1"; do set -- $V; for S in 3 4 1; do
-  AT_TWO_PASS=$1 AT_TP_SPLIT=$2 AT_DIAG_NO_WALK_KERNEL=$3 timeout -k 10 300 python3 bench.py --workload $W --steps 30 --warmup 5 --streams $S --no-cpu-baseline | python3 -c "
+  LIBV=""; [ $3 = 1 ] && LIBV=AT_LIB_PATH=$R/aligntools/c_amd/exp/libaligntools_hip_sweeponly.so
+  env $LIBV AT_TWO_PASS=$1 AT_TP_SPLIT=$2 AT_DIAG_NO_WALK_KERNEL=$3 timeout -k 10 300 python3 bench.py --workload $W --steps 30 --warmup 5 --streams $S --no-cpu-baseline | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps({'workload':'$W','AT_TWO_PASS':$1,'AT_TP_SPLIT':$2,'sweep_only':$3,'streams':$S,'gcups':round(d['value'],1),'ms_per_step':round(d['ms_per_step'],4),'kernel_config':d['config']['kernel_config']}))" >> $O/two_pass_ab.jsonl 2>> $O/bench.err
 done; done; done
 # where a launch of the walk-kernel form spends its time: rocprofv3 kernel stats one launch at a time, the start / end of every launch with three in flight
