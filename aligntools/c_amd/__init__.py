@@ -25,7 +25,7 @@ ST_LOW, ST_MID, ST_UPP = 1, 2, 3
 # every symbol include/aligntools_hip.h declares
 ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_align_batch",
                "at_align_batch_device", "at_align_allpairs_device", "at_render_batch_device", "at_compact_ops_device",
-               "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream",
+               "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream", "at_search",
                "at_comm_init", "at_comm_broadcast_scoring", "at_comm_allgather", "at_comm_destroy", "at_comm_abi_checked",
                "at_pack_words", "at_pack_batch", "at_render", "at_last_config"]
 
@@ -115,6 +115,9 @@ def load_library():
     lib.at_align_allpairs_stream.restype = C.c_int
     lib.at_align_allpairs_stream.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                              ALLPAIRS_CHUNK_FN, C.c_void_p]
+    lib.at_search.restype = C.c_int
+    lib.at_search.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_int, C.c_int, C.c_int32] + [C.c_void_p] * 6
     lib.at_comm_abi_checked.restype = C.c_int
     lib.at_comm_abi_checked.argtypes = []
     lib.at_pack_words.restype = C.c_int64
@@ -346,6 +349,36 @@ class Aligner:
         if err:
             raise err[0]
         self._check(rc)
+
+    def search(self, mode, queries, targets, k=1, cutoff=None):
+        """Every query against every target, the best `k` (1..64) hits of each query (at_search).  queries / targets: lists of
+        str or bytes.  Rank: higher score first (edit: smaller distance first), ties: smaller target index first; `cutoff` keeps
+        only hits with score >= cutoff (edit: distance <= cutoff).  fit: targets shorter than a query are not its candidates.
+        Returns a dict: target, score, end_i, end_j, state -- int32 arrays of shape (nq, k), row q = the hits of query q in rank
+        order, unused entries with target -1 -- and nhits (nq,)."""
+        if isinstance(mode, str):
+            mode = MODES[mode]
+        qs = [_b(x) for x in queries]
+        ts = [_b(x) for x in targets]
+        nq, nt = len(qs), len(ts)
+
+        def pack(seqs):
+            lens = np.fromiter((len(x) for x in seqs), dtype=np.int32, count=len(seqs))
+            off = np.zeros(len(seqs), dtype=np.int64)
+            if len(seqs) > 1:
+                np.cumsum(lens[:-1], out=off[1:])
+            return np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8).copy(), off, lens
+        qb, qo, ql = pack(qs)
+        tb, to, tl = pack(ts)
+        out = {name: np.full((nq, int(k)), -1 if name == "target" else 0, dtype=np.int32)
+               for name in ("target", "score", "end_i", "end_j", "state")}
+        nhits = np.zeros(nq, dtype=np.int32)
+        self._check(self._lib.at_search(self._h, mode, nq, _ptr(qb), _ptr(qo), _ptr(ql), nt, _ptr(tb), _ptr(to), _ptr(tl), int(k),
+                                        0 if cutoff is None else 1, 0 if cutoff is None else int(cutoff),
+                                        _ptr(out["target"]), _ptr(out["score"]), _ptr(out["end_i"]), _ptr(out["end_j"]),
+                                        _ptr(out["state"]), _ptr(nhits)))
+        out["nhits"] = nhits
+        return out
 
     def align_allpairs_device(self, mode, nreads, d_seq, bits, d_woff, d_len, max_len, first_pair, npairs, want_traceback,
                               d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream=0):

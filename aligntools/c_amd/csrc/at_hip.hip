@@ -8,6 +8,7 @@
 #include "at_pack.hip.h"
 #include "at_render.hip.h"
 #include "at_myers.hip.h"
+#include "at_search.hip.h"
 #include "../../../include/aligntools_hip.h"
 
 #include <algorithm>
@@ -2003,6 +2004,162 @@ extern "C" int at_align_allpairs_stream(at_handle *h, int mode, int64_t nreads, 
 		int rc2 = upload_reads(h, mode, nreads, seq_blob, off, len, &rs);
 		if (rc2) return rc2;
 		return allpairs_scores(h, mode, nreads, rs, first_pair, npairs, chunk_pairs, fn, user);
+	});
+}
+
+/* ---- query-vs-target search: every query against every target, the best k hits of each query kept on the device ----
+ * Queries and targets go up as ONE read set, queries first (one 2-bit / 8-bit decision for both, as all-vs-all).  The targets are
+ * sorted by length (stable), the queries grouped by length: a BLOCK is one query-length group x the run of sorted targets it may
+ * meet (fit: those no shorter than the query), cut into SLICES of at most AT_ALLPAIRS_CHUNK pairs.  Per slice, on the handle's stream
+ * and without a host round trip: at_search_desc_k writes the slice's descriptors, align_device sweeps them (a block of one query
+ * length x one target length with the uniform-shape promise: the packed kernels), at_search_merge_k folds the scores into the
+ * per-query lists (at_search.hip).  The lists come down in one copy at the end. */
+static int search_lists(at_handle *h, int mode, int64_t nq, const int32_t *q_len, int64_t nt, const int32_t *t_len, const ReadSet &rs,
+                        int k, int use_cutoff, int32_t cutoff, int32_t *out_target, int32_t *out_score, int32_t *out_end_i,
+                        int32_t *out_end_j, int32_t *out_state, int32_t *out_nhits)
+{
+	std::vector<int> qperm((size_t)nq), tperm((size_t)nt);
+	for (int64_t q = 0; q < nq; ++q) qperm[(size_t)q] = (int)q;
+	for (int64_t t = 0; t < nt; ++t) tperm[(size_t)t] = (int)t;
+	std::stable_sort(qperm.begin(), qperm.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
+	std::stable_sort(tperm.begin(), tperm.end(), [&](int a, int b) { return t_len[a] < t_len[b]; });
+	std::vector<int32_t> tls((size_t)nt);
+	for (int64_t t = 0; t < nt; ++t) tls[(size_t)t] = t_len[tperm[(size_t)t]];
+	struct Block { int qa, nqb, ta; int64_t ntb; int32_t l1, l2; bool uniform; };
+	std::vector<Block> blocks;
+	int64_t most = 0;
+	for (int64_t a = 0, b; a < nq; a = b) {
+		const int32_t L = q_len[qperm[(size_t)a]];
+		for (b = a; b < nq && q_len[qperm[(size_t)b]] == L; ++b) {}
+		const int64_t ta = mode == AT_MODE_FIT ? std::lower_bound(tls.begin(), tls.end(), L) - tls.begin() : 0;
+		if (ta == nt) continue;                                   /* fit: every target is shorter than these queries */
+		blocks.push_back({(int)a, (int)(b - a), (int)ta, nt - ta, L, tls.back(), tls[(size_t)ta] == tls.back()});
+		most = std::max<int64_t>(most, (b - a) * (nt - ta));
+	}
+	int64_t chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
+	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(std::max<int64_t>(most, 1), 1LL << 28)));
+	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	/* descriptors (24 bytes per pair of a slice) and both permutations; results (16 bytes per pair); the lists (20 bytes per entry) + flag */
+	const size_t b8 = al((size_t)chunk * 8), b4 = al((size_t)chunk * 4), bq = al((size_t)nq * 4), bt = al((size_t)nt * 4);
+	const size_t nl = (size_t)nq * (size_t)k, bkey = al(nl * 8), bl4 = al(nl * 4);
+	int rc = grow(h, &h->d_desc, &h->desc_bytes, 2 * b8 + 2 * b4 + bq + bt);
+	if (rc) return rc;
+	rc = grow(h, &h->d_out, &h->out_bytes, 4 * b4);
+	if (rc) return rc;
+	const size_t lbytes = bkey + 3 * bl4 + 256;
+	rc = grow(h, &h->d_str, &h->str_bytes, lbytes);
+	if (rc) return rc;
+	char *dd = (char *)h->d_desc, *dr = (char *)h->d_out, *dl = (char *)h->d_str;
+	int64_t *d_woff1 = (int64_t *)dd, *d_woff2 = (int64_t *)(dd + b8);
+	int32_t *d_len1 = (int32_t *)(dd + 2 * b8), *d_len2 = (int32_t *)(dd + 2 * b8 + b4);
+	int *d_qperm = (int *)(dd + 2 * b8 + 2 * b4), *d_tperm = (int *)(dd + 2 * b8 + 2 * b4 + bq);
+	int32_t *d_sc = (int32_t *)dr, *d_ei = (int32_t *)(dr + b4), *d_ej = (int32_t *)(dr + 2 * b4), *d_st = (int32_t *)(dr + 3 * b4);
+	unsigned long long *d_key = (unsigned long long *)dl;
+	int *d_lei = (int *)(dl + bkey), *d_lej = (int *)(dl + bkey + bl4), *d_lst = (int *)(dl + bkey + 2 * bl4), *d_bad = (int *)(dl + bkey + 3 * bl4);
+	hipStream_t s = h->stream;
+	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_tperm, tperm.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemsetAsync(dl, 0, lbytes, s));
+	std::string cfg0;
+	int64_t nslices = 0;
+	for (const Block &B : blocks) {
+		const int64_t bp = (int64_t)B.nqb * B.ntb;
+		for (int64_t s0 = 0; s0 < bp; s0 += chunk) {
+			const int64_t n = std::min(chunk, bp - s0);
+			at::SearchDescArgs da;
+			memset(&da, 0, sizeof da);
+			da.s0 = s0; da.n = n; da.ntb = B.ntb; da.qa = B.qa; da.ta = B.ta; da.nq = (int)nq;
+			da.qperm = d_qperm; da.tperm = d_tperm; da.swoff = (const long long *)rs.d_swoff; da.slen = rs.d_len;
+			da.woff1 = (long long *)d_woff1; da.woff2 = (long long *)d_woff2; da.len1 = d_len1; da.len2 = d_len2;
+			HIP_TRY(h, at_search_desc_launch(&da, h->ncu, s));
+			rc = align_device(h, mode, n, rs.d_words, rs.bits, d_woff1, d_len1, d_woff2, d_len2, B.l1, B.l2, B.uniform ? 1 : 0, 0,
+			                  d_sc, d_ei, d_ej, d_st, nullptr, nullptr, nullptr, s, 0, 0);
+			if (rc) { (void)hipStreamSynchronize(s); return rc; }
+			if (nslices == 0) cfg0 = h->cfg;
+			at::SearchMergeArgs ma;
+			memset(&ma, 0, sizeof ma);
+			ma.s0 = s0; ma.n = n; ma.ntb = B.ntb; ma.qa = B.qa; ma.ta = B.ta;
+			ma.nqs = (int)((s0 + n - 1) / B.ntb - s0 / B.ntb + 1);
+			ma.qperm = d_qperm; ma.tperm = d_tperm;
+			ma.score = d_sc; ma.end_i = d_ei; ma.end_j = d_ej; ma.state = d_st;
+			ma.k = k; ma.is_edit = mode == AT_MODE_EDIT; ma.use_cutoff = use_cutoff ? 1 : 0; ma.cutoff = cutoff;
+			ma.lkey = d_key; ma.lei = d_lei; ma.lej = d_lej; ma.lst = d_lst; ma.bad = d_bad;
+			HIP_TRY(h, at_search_merge_launch(&ma, s));
+			++nslices;
+		}
+	}
+	std::vector<char> hl(lbytes);
+	HIP_TRY(h, hipMemcpyAsync(hl.data(), dl, lbytes, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipStreamSynchronize(s));
+	int bad = 0;
+	memcpy(&bad, hl.data() + bkey + 3 * bl4, 4);
+	if (bad) return fail(h, AT_ERR_DOMAIN, "search: a pair outside the domain on which the reference is defined");
+	const unsigned long long *hk = (const unsigned long long *)hl.data();
+	const int32_t *hei = (const int32_t *)(hl.data() + bkey), *hej = (const int32_t *)(hl.data() + bkey + bl4), *hst = (const int32_t *)(hl.data() + bkey + 2 * bl4);
+	for (int64_t q = 0; q < nq; ++q) {
+		int nh = 0;
+		for (int j = 0; j < k; ++j) {
+			const size_t e = (size_t)q * k + j;
+			if (!hk[e]) break;
+			const int32_t r = (int32_t)((uint32_t)(hk[e] >> 32) ^ 0x80000000u);
+			out_target[e] = (int32_t)~(uint32_t)hk[e];
+			out_score[e] = mode == AT_MODE_EDIT ? -r : r;
+			out_end_i[e] = hei[e]; out_end_j[e] = hej[e]; out_state[e] = hst[e];
+			++nh;
+		}
+		out_nhits[q] = nh;
+	}
+	snprintf(h->cfg, sizeof h->cfg, "search: %lld blocks, %lld slices, k=%d; %.560s", (long long)blocks.size(), (long long)nslices, k, cfg0.c_str());
+	return AT_OK;
+}
+
+extern "C" int at_search(at_handle *h, int mode,
+                         int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+                         int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+                         int k, int use_cutoff, int32_t cutoff,
+                         int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
+                         int32_t *out_state, int32_t *out_nhits)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_search: NULL handle");
+	if (mode < AT_MODE_GLOBAL || mode > AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "unknown mode %d", mode);
+	if (nq < 0 || nt < 0) return fail(h, AT_ERR_ARG, "at_search: negative size");
+	if (k < 1 || k > 64) return fail(h, AT_ERR_ARG, "at_search: k = %d outside 1..64", k);
+	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "at_search: %lld queries + %lld targets: at most 2^31 - 1 reads", (long long)nq, (long long)nt);
+	if (nq == 0) return AT_OK;
+	if (!q_blob || !q_off || !q_len || !out_target || !out_score || !out_end_i || !out_end_j || !out_state || !out_nhits ||
+	    (nt > 0 && (!t_blob || !t_off || !t_len)))
+		return fail(h, AT_ERR_ARG, "at_search: NULL argument");
+	const bool need_base = mode == AT_MODE_LOCAL || mode == AT_MODE_OVERLAP;   /* (as upload_reads) */
+	for (int64_t q = 0; q < nq; ++q) {
+		if (q_len[q] < 0 || q_off[q] < 0) return fail(h, AT_ERR_ARG, "query %lld: negative length or offset", (long long)q);
+		if (need_base && q_len[q] < 1) return fail(h, AT_ERR_DOMAIN, "query %lld: empty", (long long)q);
+	}
+	for (int64_t t = 0; t < nt; ++t) {
+		if (t_len[t] < 0 || t_off[t] < 0) return fail(h, AT_ERR_ARG, "target %lld: negative length or offset", (long long)t);
+		if (need_base && t_len[t] < 1) return fail(h, AT_ERR_DOMAIN, "target %lld: empty", (long long)t);
+	}
+	return guarded(h, "at_search", [&]() -> int {
+		for (int64_t e = 0; e < nq * k; ++e) { out_target[e] = -1; out_score[e] = 0; out_end_i[e] = 0; out_end_j[e] = 0; out_state[e] = 0; }
+		for (int64_t q = 0; q < nq; ++q) out_nhits[q] = 0;
+		if (nt == 0) { snprintf(h->cfg, sizeof h->cfg, "search: 0 blocks, 0 slices, k=%d; ", k); return (int)AT_OK; }
+		/* one read set: the queries' and the targets' bytes side by side (a copy of the input, small beside the sweep) */
+		int64_t bytes = 0;
+		for (int64_t q = 0; q < nq; ++q) bytes += q_len[q];
+		for (int64_t t = 0; t < nt; ++t) bytes += t_len[t];
+		std::vector<uint8_t> blob((size_t)bytes + 32);
+		std::vector<int64_t> off((size_t)(nq + nt));
+		std::vector<int32_t> len((size_t)(nq + nt));
+		int64_t at = 0;
+		for (int64_t r = 0; r < nq + nt; ++r) {
+			const bool isq = r < nq;
+			const int32_t l = isq ? q_len[r] : t_len[r - nq];
+			if (l) memcpy(blob.data() + at, isq ? q_blob + q_off[r] : t_blob + t_off[r - nq], (size_t)l);
+			off[(size_t)r] = at; len[(size_t)r] = l; at += l;
+		}
+		ReadSet rs;
+		int rc = upload_reads(h, mode, nq + nt, blob.data(), off.data(), len.data(), &rs);
+		if (rc) return rc;
+		return search_lists(h, mode, nq, q_len, nt, t_len, rs, k, use_cutoff, cutoff, out_target, out_score, out_end_i, out_end_j, out_state, out_nhits);
 	});
 }
 

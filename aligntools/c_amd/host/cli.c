@@ -7,6 +7,8 @@
  * Extension (absent from the reference, does not change the five commands):
  *   alignTools batch <command> [options] <pairs.fa>
  *     records (2k, 2k+1) of the file form pair k; all pairs go to the GPU in one batch.
+ *   alignTools batch <command> [options] --queries <queries.fa> [--best K] <targets.fa>
+ *     every query against every target; the best K hits of each query are printed.
  */
 #define _POSIX_C_SOURCE 200809L
 #include "at_host.h"
@@ -127,6 +129,11 @@ static int main_single(int cmd, int argc, char *argv[])
  *     --score-only   no tracebacks: one line per pair (name1, name2, score)
  *     --min-score T  (overlap --all-vs-all --score-only) only pairs that score at least T are printed; pairs the bit-parallel
  *                    bound proves below T are not swept at all (at_set_min_score)
+ *     --queries Q    every record of Q (a query) against every record of the file (a target); per query, in file order, its best
+ *                    --best K (1..64, default 1) hits in rank order -- higher score first, edit: smaller distance first, ties: the
+ *                    earlier target -- each printed as a pair line of this command (at_search; strings from at_align_batch_strings
+ *                    on the hit pairs).  --min-score T (not for edit) keeps hits that score at least T.  fit: targets shorter than
+ *                    a query are not its hits; -s takes the site list from the first target's comment.  One GPU.
  *     --gpus N       one process per GPU: this process starts N workers (itself, with AT_RANK / AT_WORLD / AT_DEVICE /
  *                    AT_COMM_DIR in their environment), rank 0's options are broadcast over RCCL, every rank aligns a
  *                    contiguous share of the pairs on its own GPU, results are gathered over RCCL and rank 0 prints them
@@ -135,7 +142,7 @@ static int main_single(int cmd, int argc, char *argv[])
  * thread -- which also pays the HIP start-up, in the shadow of the first chunks' parsing -- sends each chunk to the GPU
  * and writes its results with one fwrite.  Memory is bounded by the chunks in flight, whatever the size of the file;
  * --all-vs-all keeps the read set and streams slices of the triangle instead (at_align_allpairs_stream). */
-typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; } batch_flags;
+typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set; } batch_flags;
 
 /* linear index p of the strict upper triangle of n x n (row-major) -> (a, b), a < b: closed form + integer correction */
 static void tri_seek(int64_t p, int64_t n, int64_t *a, int64_t *b)
@@ -567,6 +574,77 @@ static int batch_worker(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	return 0;
 }
 
+/* ---- --queries: every query against every record of the target file, the best K hits of each query (at_search) ----
+ * Both files are read into one record set (queries first): the hit pairs' strings come from one at_align_batch_strings call on
+ * the same blob. */
+static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *qfile, const char *tfile)
+{
+	at_reader *rq = at_reader_open(qfile), *rt;
+	at_chunk c;
+	at_handle *h;
+	slice_t w;
+	tbuf out = {NULL, 0, 0};
+	int64_t nq, nt, q, x, nhit = 0, *qoff, *toff;
+	int32_t *qlen, *tlen, *tgt, *sc, *ei, *ej, *st, *nh;
+	int rc, j;
+	const int tb = !bf->score_only && cmd != C_EDIT, kb = bf->best;
+	const int mode = cmd == C_GLOBAL ? AT_MODE_GLOBAL : cmd == C_LOCAL ? AT_MODE_LOCAL : cmd == C_FIT ? AT_MODE_FIT
+	               : cmd == C_OVERLAP ? AT_MODE_OVERLAP : AT_MODE_EDIT;
+	if (!rq) die("Can't open %s\n", qfile);
+	rt = at_reader_open(tfile);
+	if (!rt) die("Can't open %s\n", tfile);
+	memset(&c, 0, sizeof c);
+	memset(&w, 0, sizeof w);
+	while (at_reader_read(rq, (size_t)-1, (size_t)-1, &c) > 0) {}
+	nq = (int64_t)c.n;
+	while (at_reader_read(rt, (size_t)-1, (size_t)-1, &c) > 0) {}
+	nt = (int64_t)c.n - nq;
+	at_reader_close(rq); at_reader_close(rt);
+	if (opt->s == AT_TRUE) {      /* (as `batch fit -s` takes them from record 1, the first pair's second sequence) */
+		if (nt < 1 || c.comment_off[nq] == (size_t)-1) die("fail to read junction sites");
+		opt->sites.size = (size_t)at_parse_sites(c.comments + c.comment_off[nq], &opt->sites.pos);
+	}
+	if (nq == 0 || nt == 0) { at_chunk_free(&c); return 0; }
+	h = at_host_handle();
+	rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, opt->s == AT_TRUE, opt->sites.pos, (int)opt->sites.size);
+	if (rc != AT_OK) die("%s", at_last_error(h));
+	qoff = (int64_t *)at_xmalloc((size_t)nq * 8); qlen = (int32_t *)at_xmalloc((size_t)nq * 4);
+	toff = (int64_t *)at_xmalloc((size_t)nt * 8); tlen = (int32_t *)at_xmalloc((size_t)nt * 4);
+	for (q = 0; q < nq; ++q) { qoff[q] = (int64_t)c.off[q]; qlen[q] = (int32_t)c.len[q]; }
+	for (x = 0; x < nt; ++x) { toff[x] = (int64_t)c.off[nq + x]; tlen[x] = (int32_t)c.len[nq + x]; }
+	tgt = (int32_t *)at_xmalloc((size_t)nq * kb * 4); sc = (int32_t *)at_xmalloc((size_t)nq * kb * 4);
+	ei = (int32_t *)at_xmalloc((size_t)nq * kb * 4); ej = (int32_t *)at_xmalloc((size_t)nq * kb * 4);
+	st = (int32_t *)at_xmalloc((size_t)nq * kb * 4); nh = (int32_t *)at_xmalloc((size_t)nq * 4);
+	trace("search: records read, queries", nq);
+	rc = at_search(h, mode, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, bf->min_on, bf->min_score, tgt, sc, ei, ej, st, nh);
+	if (rc != AT_OK) die("%s", at_last_error(h));
+	trace("search: done, queries", nq);
+	for (q = 0; q < nq; ++q) nhit += nh[q];
+	if (tb && nhit > 0) {
+		slice_reserve(&w, nhit);
+		x = 0;
+		for (q = 0; q < nq; ++q)
+			for (j = 0; j < nh[q]; ++j, ++x) {
+				const int64_t t = nq + tgt[q * kb + j];
+				w.off1[x] = qoff[q]; w.l1[x] = qlen[q]; w.off2[x] = (int64_t)c.off[t]; w.l2[x] = (int32_t)c.len[t];
+			}
+		slice_run(&w, h, cmd, 1, c.blob, nhit);
+		trace("search: hit strings rendered, hits", nhit);
+	}
+	x = 0;
+	for (q = 0; q < nq; ++q) {
+		for (j = 0; j < nh[q]; ++j, ++x)
+			tb_pair(&out, c.names + c.name_off[q], c.names + c.name_off[nq + tgt[q * kb + j]], sc[q * kb + j], cmd == C_EDIT,
+			        tb ? w.r1 + w.slot[x] : NULL, tb ? w.r2 + w.slot[x] : NULL, tb ? (size_t)w.nops[x] : 0);
+		if (out.l > ((size_t)8 << 20)) tb_flush(&out);
+	}
+	tb_flush(&out);
+	free(out.s); free(qoff); free(qlen); free(toff); free(tlen); free(tgt); free(sc); free(ei); free(ej); free(st); free(nh);
+	slice_free(&w);
+	at_chunk_free(&c);
+	return 0;
+}
+
 /* start one worker per GPU (this binary again, told its rank through the environment) and wait for them */
 static int batch_launch(int world, char *argv0, int argc, char *argv[])
 {
@@ -626,26 +704,44 @@ static int main_batch(int argc, char *argv[], char *argv0)
 {
 	int cmd = -1, k, n = 0;
 	opt_t *opt = init_opt();
-	batch_flags bf = {0, 0, 1, 0, 0};
+	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0};
 	char **av = (char **)at_xmalloc((size_t)(argc + 1) * sizeof(char *));
-	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] <pairs.fa>\n";
+	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] <pairs.fa>\n"
+	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--min-score T] [--score-only] <targets.fa>\n";
 	/* the long flags of the extension are taken out before getopt sees the reference's short options */
 	for (k = 0; k < argc; ++k) {
 		if (strcmp(argv[k], "--score-only") == 0) bf.score_only = 1;
 		else if (strcmp(argv[k], "--all-vs-all") == 0) bf.all_vs_all = 1;
 		else if (strcmp(argv[k], "--gpus") == 0 && k + 1 < argc) bf.gpus = atoi(argv[++k]);
 		else if (strcmp(argv[k], "--min-score") == 0 && k + 1 < argc) { bf.min_on = 1; bf.min_score = atoi(argv[++k]); }
+		else if (strcmp(argv[k], "--queries") == 0 && k + 1 < argc) bf.queries = argv[++k];
+		else if (strcmp(argv[k], "--best") == 0 && k + 1 < argc) { bf.best = atoi(argv[++k]); bf.best_set = 1; }
 		else av[n++] = argv[k];
 	}
 	av[n] = NULL;
 	if (n < 2 || bf.gpus < 1 || bf.gpus > 64) { fprintf(stderr, "%s", usage_line); free(opt); free(av); return 1; }
 	for (k = 0; k < 5; ++k) if (strcmp(av[1], cmd_name[k]) == 0) cmd = k;
 	if (cmd < 0) { fprintf(stderr, "[main] unrecognized command '%s'\n", av[1]); free(opt); free(av); return 1; }
-	if (bf.min_on && !(cmd == C_OVERLAP && bf.all_vs_all && bf.score_only)) {
+	/* --queries: refused with what it cannot go with, before any GPU call */
+	{
+		const char *why = NULL;
+		if (bf.queries && bf.all_vs_all) why = "--queries does not go with --all-vs-all (a search aligns queries against targets)";
+		else if (bf.queries && bf.gpus > 1) why = "--queries runs on one GPU: it does not go with --gpus N > 1";
+		else if (bf.queries && bf.min_on && cmd == C_EDIT) why = "--min-score does not go with `batch edit --queries` (edit ranks by distance)";
+		else if (bf.best_set && !bf.queries) why = "--best goes with --queries";
+		else if (bf.queries && (bf.best < 1 || bf.best > 64)) why = "--best K needs 1 <= K <= 64";
+		if (why) { fprintf(stderr, "%s\n%s", why, usage_line); free(opt); free(av); return 1; }
+	}
+	if (bf.min_on && !bf.queries && !(cmd == C_OVERLAP && bf.all_vs_all && bf.score_only)) {
 		fprintf(stderr, "--min-score goes with `batch overlap --all-vs-all --score-only`\n%s", usage_line); free(opt); free(av); return 1;
 	}
 	if (parse_opts(cmd, n - 1, av + 1, opt)) { free(opt); free(av); return 1; }
 	if (optind + 1 > n - 1) { cmd_usage(cmd, opt); free(opt); free(av); return 1; }
+	if (bf.queries) {
+		k = batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
+		free(opt->sites.pos); free(opt); free(av);
+		return k;
+	}
 	if (bf.gpus > 1 && !getenv("AT_RANK")) {        /* the launcher: never touches a GPU itself */
 		k = batch_launch(bf.gpus, argv0, argc, argv);
 		free(opt); free(av);

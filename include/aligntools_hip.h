@@ -185,6 +185,26 @@ int at_align_allpairs_stream(at_handle *h, int mode, int64_t nreads,
                              at_allpairs_chunk_fn fn, void *user);
 
 /*
+ * Every query against every target: for each query q the best k hits (1 <= k <= 64) in rank order.
+ *   queries q_off/q_len in q_blob, targets t_off/t_len in t_blob (host memory, any alphabet, like at_align_batch)
+ *   rank: the four affine modes: higher score first; AT_MODE_EDIT: smaller distance first; ties: smaller target index first
+ *   use_cutoff != 0: only hits that rank at least as well as `cutoff` (score >= cutoff; edit: distance <= cutoff)
+ *   out_* hold nq*k entries, row q = hits of query q; out_nhits[q] <= k; unused entries have target -1
+ *   score / end_i / end_j / state of a hit are exactly what at_align_batch returns for that (query, target) pair
+ *   AT_MODE_FIT: a pair whose query is longer than its target is not a candidate (no error); with use_jump the
+ *   handle's site list applies to every target, as in a pair-list batch
+ * Synchronous; no tracebacks (pass the hit pairs to at_align_batch / at_align_batch_strings for those).  Queries and targets go up
+ * as one read set; only the nq*k list entries come back.  at_set_min_score does not apply to a search.  nq == 0 writes nothing;
+ * nt == 0 gives every query 0 hits.  at_last_config: "search: B blocks, S slices, k=K; " and the first slice's sweep.
+ */
+int at_search(at_handle *h, int mode,
+              int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+              int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+              int k, int use_cutoff, int32_t cutoff,
+              int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
+              int32_t *out_state, int32_t *out_nhits);
+
+/*
  * Output rendering on the GPU: what trace_back_* + strrev produce (alignment.h:372-412,
  * 558-592, 766-800, 896-922, 172-184) -- the two gapped strings, in reading order -- from the op codes and end
  * cells at_align_batch_device left in HBM and the same packed sequences.  Pair k's strings are written to
