@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("AT_LIB_PATH") or os.path.join(HERE, "libaligntools_hi
 
 MODE_GLOBAL, MODE_LOCAL, MODE_FIT, MODE_OVERLAP, MODE_EDIT = 0, 1, 2, 3, 4
 MODES = {"global": MODE_GLOBAL, "local": MODE_LOCAL, "fit": MODE_FIT, "overlap": MODE_OVERLAP, "edit": MODE_EDIT}
+STRAND_FWD, STRAND_REV, STRAND_BOTH = 1, 2, 3
+STRANDS = {"forward": STRAND_FWD, "reverse": STRAND_REV, "both": STRAND_BOTH}
 OP_MID, OP_LOW, OP_UPP, OP_JUMP = 0, 1, 2, 3
 ST_LOW, ST_MID, ST_UPP = 1, 2, 3
 
@@ -26,6 +28,7 @@ ST_LOW, ST_MID, ST_UPP = 1, 2, 3
 ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_align_batch",
                "at_align_batch_device", "at_align_allpairs_device", "at_render_batch_device", "at_compact_ops_device",
                "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream", "at_search",
+               "at_search_strands", "at_revcomp", "at_revcomp_device",
                "at_comm_init", "at_comm_broadcast_scoring", "at_comm_allgather", "at_comm_destroy", "at_comm_abi_checked",
                "at_pack_words", "at_pack_batch", "at_render", "at_last_config"]
 
@@ -118,6 +121,13 @@ def load_library():
     lib.at_search.restype = C.c_int
     lib.at_search.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_int, C.c_int, C.c_int32] + [C.c_void_p] * 6
+    lib.at_search_strands.restype = C.c_int
+    lib.at_search_strands.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int] + [C.c_void_p] * 7
+    lib.at_revcomp.restype = C.c_int
+    lib.at_revcomp.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.at_revcomp_device.restype = C.c_int
+    lib.at_revcomp_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.at_comm_abi_checked.restype = C.c_int
     lib.at_comm_abi_checked.argtypes = []
     lib.at_pack_words.restype = C.c_int64
@@ -181,6 +191,18 @@ def pack_pairs(pairs, bits=0):
     if rc:
         raise AlignToolsError(rc, lib.at_last_error(None).decode())
     return words, woff1, woff2, len1, len2, b.value
+
+
+def revcomp(s):
+    """Host helper: the reverse complement of a str / bytes as bytes (at_revcomp: IUPAC codes in both letter cases, every
+    other byte unchanged)."""
+    lib = load_library()
+    s = _b(s)
+    out = C.create_string_buffer(len(s) + 1)
+    rc = lib.at_revcomp(s, len(s), out)
+    if rc:
+        raise AlignToolsError(rc, lib.at_last_error(None).decode())
+    return out.raw[:len(s)]
 
 
 def _flatten(pairs):
@@ -350,14 +372,24 @@ class Aligner:
             raise err[0]
         self._check(rc)
 
-    def search(self, mode, queries, targets, k=1, cutoff=None):
+    def revcomp_device(self, nseq, d_seq, bits, d_woff, d_len, d_out, d_out_woff=None, stream=0):
+        """Raw device-pointer entry of the reverse-complement kernel for packed reads (at_revcomp_device)."""
+        self._check(self._lib.at_revcomp_device(self._h, nseq, d_seq, bits, d_woff, d_len, d_out, d_out_woff, stream))
+
+    def search(self, mode, queries, targets, k=1, cutoff=None, strands="forward"):
         """Every query against every target, the best `k` (1..64) hits of each query (at_search).  queries / targets: lists of
         str or bytes.  Rank: higher score first (edit: smaller distance first), ties: smaller target index first; `cutoff` keeps
         only hits with score >= cutoff (edit: distance <= cutoff).  fit: targets shorter than a query are not its candidates.
         Returns a dict: target, score, end_i, end_j, state -- int32 arrays of shape (nq, k), row q = the hits of query q in rank
-        order, unused entries with target -1 -- and nhits (nq,)."""
+        order, unused entries with target -1 -- and nhits (nq,).
+        strands: "forward" (the queries as given), "reverse" (their reverse complements, made on the device) or "both"
+        (at_search_strands).  With "reverse" / "both" a hit is (target, strand) and the dict also holds `strand` (nq, k): 0 = the
+        query as given, 1 = its reverse complement (score, end cell and state are those of align_batch on (revcomp(query),
+        target)), -1 = unused; ties on score and target rank strand 0 first."""
         if isinstance(mode, str):
             mode = MODES[mode]
+        if strands not in STRANDS:
+            raise ValueError("strands must be one of %s" % ", ".join(sorted(STRANDS)))
         qs = [_b(x) for x in queries]
         ts = [_b(x) for x in targets]
         nq, nt = len(qs), len(ts)
@@ -373,6 +405,14 @@ class Aligner:
         out = {name: np.full((nq, int(k)), -1 if name == "target" else 0, dtype=np.int32)
                for name in ("target", "score", "end_i", "end_j", "state")}
         nhits = np.zeros(nq, dtype=np.int32)
+        if strands != "forward":
+            out["strand"] = np.full((nq, int(k)), -1, dtype=np.int32)
+            self._check(self._lib.at_search_strands(self._h, mode, nq, _ptr(qb), _ptr(qo), _ptr(ql), nt, _ptr(tb), _ptr(to), _ptr(tl),
+                                                    int(k), 0 if cutoff is None else 1, 0 if cutoff is None else int(cutoff),
+                                                    STRANDS[strands], _ptr(out["target"]), _ptr(out["score"]), _ptr(out["end_i"]),
+                                                    _ptr(out["end_j"]), _ptr(out["state"]), _ptr(out["strand"]), _ptr(nhits)))
+            out["nhits"] = nhits
+            return out
         self._check(self._lib.at_search(self._h, mode, nq, _ptr(qb), _ptr(qo), _ptr(ql), nt, _ptr(tb), _ptr(to), _ptr(tl), int(k),
                                         0 if cutoff is None else 1, 0 if cutoff is None else int(cutoff),
                                         _ptr(out["target"]), _ptr(out["score"]), _ptr(out["end_i"]), _ptr(out["end_j"]),

@@ -9,6 +9,7 @@
 #include "at_render.hip.h"
 #include "at_myers.hip.h"
 #include "at_search.hip.h"
+#include "at_revcomp.hip.h"
 #include "../../../include/aligntools_hip.h"
 
 #include <algorithm>
@@ -1858,11 +1859,15 @@ struct ReadSet {
 	int bits = 2, maxlen = 0;
 };
 
-static int upload_reads(at_handle *h, int mode, int64_t nreads, const uint8_t *seq_blob, const int64_t *off, const int32_t *len, ReadSet *rs)
+/* nrev > 0: the read set also gets, as reads nreads .. nreads + nrev - 1, the reverse complements of reads 0 .. nrev - 1, made on the
+ * device from their packed words (at_revcomp.hip) behind the pack kernel: no byte goes up twice */
+static int upload_reads(at_handle *h, int mode, int64_t nreads, const uint8_t *seq_blob, const int64_t *off, const int32_t *len, ReadSet *rs,
+                        int64_t nrev = 0)
 {
 	int maxlen = 0;
+	const int64_t ntot = nreads + nrev;
 	int64_t blob_lo = INT64_MAX, blob_bytes = 0, nwords2 = 0, nwords8 = 0;
-	std::vector<int64_t> soff((size_t)nreads), swoff2((size_t)nreads), swoff8((size_t)nreads);
+	std::vector<int64_t> soff((size_t)nreads), swoff2((size_t)ntot), swoff8((size_t)ntot);
 	for (int64_t k = 0; k < nreads; ++k) {
 		if (len[k] < 0 || off[k] < 0) return fail(h, AT_ERR_ARG, "read %lld: negative length or offset", (long long)k);
 		if ((mode == AT_MODE_LOCAL || mode == AT_MODE_OVERLAP) && len[k] < 1) return fail(h, AT_ERR_DOMAIN, "read %lld: empty", (long long)k);
@@ -1875,10 +1880,14 @@ static int upload_reads(at_handle *h, int mode, int64_t nreads, const uint8_t *s
 		swoff8[(size_t)k] = nwords8; nwords8 += (len[k] + 3) / 4 + 1;
 		blob_bytes = std::max<int64_t>(blob_bytes, soff[(size_t)k] + len[k]);
 	}
+	for (int64_t k = 0; k < nrev; ++k) {
+		swoff2[(size_t)(nreads + k)] = nwords2; nwords2 += (len[k] + 15) / 16 + 1;
+		swoff8[(size_t)(nreads + k)] = nwords8; nwords8 += (len[k] + 3) / 4 + 1;
+	}
 	HIP_TRY(h, hipSetDevice(h->device));
 	drop_stale_error();
 	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t b_words = al((size_t)(std::max(nwords2, nwords8) + 4) * 4), b_off = al((size_t)nreads * 8), b_len = al((size_t)nreads * 4);
+	const size_t b_words = al((size_t)(std::max(nwords2, nwords8) + 4) * 4), b_off = al((size_t)ntot * 8), b_len = al((size_t)ntot * 4);
 	const size_t b_blob = al((size_t)blob_bytes + 32);   /* (at_pack reads whole dwords: up to 20 bytes behind the last base) */
 	int rc = grow(h, &h->d_in, &h->in_bytes, b_words + 2 * b_off + b_len + 256 + b_blob);
 	if (rc) return rc;
@@ -1892,6 +1901,7 @@ static int upload_reads(at_handle *h, int mode, int64_t nreads, const uint8_t *s
 	HIP_TRY(h, hipMemcpyAsync(d_blob, seq_blob + blob_lo, (size_t)blob_bytes, hipMemcpyHostToDevice, s));
 	HIP_TRY(h, hipMemcpyAsync(d_soff, soff.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, s));
 	HIP_TRY(h, hipMemcpyAsync(d_len, len, (size_t)nreads * 4, hipMemcpyHostToDevice, s));
+	if (nrev) HIP_TRY(h, hipMemcpyAsync(d_len + nreads, d_len, (size_t)nrev * 4, hipMemcpyDeviceToDevice, s));
 	at::PackArgs pa;
 	pa.nseq = nreads; pa.blob = d_blob; pa.off = (const long long *)d_soff; pa.len = d_len;
 	pa.woff = (const long long *)d_swoff; pa.words = d_words; pa.not_acgt = d_flag;
@@ -1899,17 +1909,23 @@ static int upload_reads(at_handle *h, int mode, int64_t nreads, const uint8_t *s
 	int bits = scores_fit_byte(h, mode) ? 2 : 8, flag = 0;
 	if (bits == 2) {
 		HIP_TRY(h, hipMemsetAsync(d_flag, 0, 4, s));
-		HIP_TRY(h, hipMemcpyAsync(d_swoff, swoff2.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, s));
+		HIP_TRY(h, hipMemcpyAsync(d_swoff, swoff2.data(), (size_t)ntot * 8, hipMemcpyHostToDevice, s));
 		hipLaunchKernelGGL(at::at_pack<2>, dim3(pgrid), dim3(256), 0, s, pa);
 		HIP_TRY(h, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(h, hipStreamSynchronize(s));
 		if (flag) bits = 8;
 	}
 	if (bits == 8) {
-		HIP_TRY(h, hipMemcpyAsync(d_swoff, swoff8.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, s));
+		HIP_TRY(h, hipMemcpyAsync(d_swoff, swoff8.data(), (size_t)ntot * 8, hipMemcpyHostToDevice, s));
 		hipLaunchKernelGGL(at::at_pack<8>, dim3(pgrid), dim3(256), 0, s, pa);
 	}
 	HIP_TRY(h, hipGetLastError());
+	if (nrev) {
+		at::RevcompArgs ra;
+		ra.nseq = nrev; ra.seq = d_words; ra.woff = (const long long *)d_swoff; ra.len = d_len;
+		ra.out = d_words; ra.out_woff = (const long long *)(d_swoff + nreads);   /* (the reverse reads' words lie behind every forward read's) */
+		HIP_TRY(h, at_revcomp_launch(&ra, bits, h->ncu, s));
+	}
 	HIP_TRY(h, hipStreamSynchronize(s));   /* swoff* are stack-lifetime vectors */
 	rs->d_words = d_words; rs->d_swoff = d_swoff; rs->d_len = d_len; rs->bits = bits; rs->maxlen = maxlen;
 	return AT_OK;
@@ -2014,33 +2030,44 @@ extern "C" int at_align_allpairs_stream(at_handle *h, int mode, int64_t nreads, 
  * and without a host round trip: at_search_desc_k writes the slice's descriptors, align_device sweeps them (a block of one query
  * length x one target length with the uniform-shape promise: the packed kernels), at_search_merge_k folds the scores into the
  * per-query lists (at_search.hip).  The lists come down in one copy at the end. */
+static const char *strands_text(int strands) { return strands == AT_STRAND_REV ? ", strands=rev" : strands == AT_STRAND_BOTH ? ", strands=both" : ""; }
+
 static int search_lists(at_handle *h, int mode, int64_t nq, const int32_t *q_len, int64_t nt, const int32_t *t_len, const ReadSet &rs,
-                        int k, int use_cutoff, int32_t cutoff, int32_t *out_target, int32_t *out_score, int32_t *out_end_i,
-                        int32_t *out_end_j, int32_t *out_state, int32_t *out_nhits)
+                        int k, int use_cutoff, int32_t cutoff, int strands, int32_t *out_target, int32_t *out_score, int32_t *out_end_i,
+                        int32_t *out_end_j, int32_t *out_state, int32_t *out_strand, int32_t *out_nhits)
 {
-	std::vector<int> qperm((size_t)nq), tperm((size_t)nt);
-	for (int64_t q = 0; q < nq; ++q) qperm[(size_t)q] = (int)q;
+	/* strands: with a reverse strand an entry of the query order is (query << 1) | strand (at_search.hip.h); with both, a query's
+	 * two entries are adjacent, strand 0 first: same length, same block, and one run of candidates for the merge */
+	const int enc = strands != AT_STRAND_FWD, two = strands == AT_STRAND_BOTH;
+	const int64_t nv = nq << two;
+	std::vector<int> qs((size_t)nq), qperm((size_t)nv), tperm((size_t)nt);
+	for (int64_t q = 0; q < nq; ++q) qs[(size_t)q] = (int)q;
 	for (int64_t t = 0; t < nt; ++t) tperm[(size_t)t] = (int)t;
-	std::stable_sort(qperm.begin(), qperm.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
+	std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
 	std::stable_sort(tperm.begin(), tperm.end(), [&](int a, int b) { return t_len[a] < t_len[b]; });
+	for (int64_t q = 0; q < nq; ++q) {
+		const int c = qs[(size_t)q];
+		if (two) { qperm[(size_t)(2 * q)] = c << 1; qperm[(size_t)(2 * q + 1)] = (c << 1) | 1; }
+		else qperm[(size_t)q] = enc ? (c << 1) | 1 : c;
+	}
 	std::vector<int32_t> tls((size_t)nt);
 	for (int64_t t = 0; t < nt; ++t) tls[(size_t)t] = t_len[tperm[(size_t)t]];
 	struct Block { int qa, nqb, ta; int64_t ntb; int32_t l1, l2; bool uniform; };
 	std::vector<Block> blocks;
 	int64_t most = 0;
 	for (int64_t a = 0, b; a < nq; a = b) {
-		const int32_t L = q_len[qperm[(size_t)a]];
-		for (b = a; b < nq && q_len[qperm[(size_t)b]] == L; ++b) {}
+		const int32_t L = q_len[qs[(size_t)a]];
+		for (b = a; b < nq && q_len[qs[(size_t)b]] == L; ++b) {}
 		const int64_t ta = mode == AT_MODE_FIT ? std::lower_bound(tls.begin(), tls.end(), L) - tls.begin() : 0;
 		if (ta == nt) continue;                                   /* fit: every target is shorter than these queries */
-		blocks.push_back({(int)a, (int)(b - a), (int)ta, nt - ta, L, tls.back(), tls[(size_t)ta] == tls.back()});
-		most = std::max<int64_t>(most, (b - a) * (nt - ta));
+		blocks.push_back({(int)(a << two), (int)((b - a) << two), (int)ta, nt - ta, L, tls.back(), tls[(size_t)ta] == tls.back()});
+		most = std::max<int64_t>(most, ((b - a) << two) * (nt - ta));
 	}
 	int64_t chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
 	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(std::max<int64_t>(most, 1), 1LL << 28)));
 	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
 	/* descriptors (24 bytes per pair of a slice) and both permutations; results (16 bytes per pair); the lists (20 bytes per entry) + flag */
-	const size_t b8 = al((size_t)chunk * 8), b4 = al((size_t)chunk * 4), bq = al((size_t)nq * 4), bt = al((size_t)nt * 4);
+	const size_t b8 = al((size_t)chunk * 8), b4 = al((size_t)chunk * 4), bq = al((size_t)nv * 4), bt = al((size_t)nt * 4);
 	const size_t nl = (size_t)nq * (size_t)k, bkey = al(nl * 8), bl4 = al(nl * 4);
 	int rc = grow(h, &h->d_desc, &h->desc_bytes, 2 * b8 + 2 * b4 + bq + bt);
 	if (rc) return rc;
@@ -2057,7 +2084,7 @@ static int search_lists(at_handle *h, int mode, int64_t nq, const int32_t *q_len
 	unsigned long long *d_key = (unsigned long long *)dl;
 	int *d_lei = (int *)(dl + bkey), *d_lej = (int *)(dl + bkey + bl4), *d_lst = (int *)(dl + bkey + 2 * bl4), *d_bad = (int *)(dl + bkey + 3 * bl4);
 	hipStream_t s = h->stream;
-	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nv * 4, hipMemcpyHostToDevice, s));
 	HIP_TRY(h, hipMemcpyAsync(d_tperm, tperm.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
 	HIP_TRY(h, hipMemsetAsync(dl, 0, lbytes, s));
 	std::string cfg0;
@@ -2068,7 +2095,7 @@ static int search_lists(at_handle *h, int mode, int64_t nq, const int32_t *q_len
 			const int64_t n = std::min(chunk, bp - s0);
 			at::SearchDescArgs da;
 			memset(&da, 0, sizeof da);
-			da.s0 = s0; da.n = n; da.ntb = B.ntb; da.qa = B.qa; da.ta = B.ta; da.nq = (int)nq;
+			da.s0 = s0; da.n = n; da.ntb = B.ntb; da.qa = B.qa; da.ta = B.ta; da.nq = (int)nq; da.enc = enc; da.nrev0 = (int)(nq + nt);
 			da.qperm = d_qperm; da.tperm = d_tperm; da.swoff = (const long long *)rs.d_swoff; da.slen = rs.d_len;
 			da.woff1 = (long long *)d_woff1; da.woff2 = (long long *)d_woff2; da.len1 = d_len1; da.len2 = d_len2;
 			HIP_TRY(h, at_search_desc_launch(&da, h->ncu, s));
@@ -2079,7 +2106,8 @@ static int search_lists(at_handle *h, int mode, int64_t nq, const int32_t *q_len
 			at::SearchMergeArgs ma;
 			memset(&ma, 0, sizeof ma);
 			ma.s0 = s0; ma.n = n; ma.ntb = B.ntb; ma.qa = B.qa; ma.ta = B.ta;
-			ma.nqs = (int)((s0 + n - 1) / B.ntb - s0 / B.ntb + 1);
+			ma.enc = enc; ma.two = two;
+			ma.nqs = (int)((s0 + n - 1) / (B.ntb << two) - s0 / (B.ntb << two) + 1);
 			ma.qperm = d_qperm; ma.tperm = d_tperm;
 			ma.score = d_sc; ma.end_i = d_ei; ma.end_j = d_ej; ma.state = d_st;
 			ma.k = k; ma.is_edit = mode == AT_MODE_EDIT; ma.use_cutoff = use_cutoff ? 1 : 0; ma.cutoff = cutoff;
@@ -2102,32 +2130,39 @@ static int search_lists(at_handle *h, int mode, int64_t nq, const int32_t *q_len
 			const size_t e = (size_t)q * k + j;
 			if (!hk[e]) break;
 			const int32_t r = (int32_t)((uint32_t)(hk[e] >> 32) ^ 0x80000000u);
-			out_target[e] = (int32_t)~(uint32_t)hk[e];
+			const uint32_t low = ~(uint32_t)hk[e];
+			out_target[e] = (int32_t)(low >> enc);
+			if (out_strand) out_strand[e] = enc ? (int32_t)(low & 1u) : 0;
 			out_score[e] = mode == AT_MODE_EDIT ? -r : r;
 			out_end_i[e] = hei[e]; out_end_j[e] = hej[e]; out_state[e] = hst[e];
 			++nh;
 		}
 		out_nhits[q] = nh;
 	}
-	snprintf(h->cfg, sizeof h->cfg, "search: %lld blocks, %lld slices, k=%d; %.560s", (long long)blocks.size(), (long long)nslices, k, cfg0.c_str());
+	snprintf(h->cfg, sizeof h->cfg, "search: %lld blocks, %lld slices, k=%d%s; %.560s", (long long)blocks.size(), (long long)nslices, k,
+	         strands_text(strands), cfg0.c_str());
 	return AT_OK;
 }
 
-extern "C" int at_search(at_handle *h, int mode,
-                         int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
-                         int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
-                         int k, int use_cutoff, int32_t cutoff,
-                         int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
-                         int32_t *out_state, int32_t *out_nhits)
+extern "C" int at_search_strands(at_handle *h, int mode,
+                                 int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+                                 int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+                                 int k, int use_cutoff, int32_t cutoff, int strands,
+                                 int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
+                                 int32_t *out_state, int32_t *out_strand, int32_t *out_nhits)
 {
 	if (!h) return fail(nullptr, AT_ERR_ARG, "at_search: NULL handle");
 	if (mode < AT_MODE_GLOBAL || mode > AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "unknown mode %d", mode);
 	if (nq < 0 || nt < 0) return fail(h, AT_ERR_ARG, "at_search: negative size");
 	if (k < 1 || k > 64) return fail(h, AT_ERR_ARG, "at_search: k = %d outside 1..64", k);
+	if (strands < AT_STRAND_FWD || strands > AT_STRAND_BOTH) return fail(h, AT_ERR_ARG, "at_search: strands = %d outside 1..3", strands);
+	const bool rev = strands != AT_STRAND_FWD;
 	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "at_search: %lld queries + %lld targets: at most 2^31 - 1 reads", (long long)nq, (long long)nt);
+	if (rev && (nt >= (1LL << 30) || 2 * nq + nt >= (1LL << 31)))
+		return fail(h, AT_ERR_ARG, "at_search: %lld queries, %lld targets: a reverse strand needs nt < 2^30 and 2 nq + nt < 2^31", (long long)nq, (long long)nt);
 	if (nq == 0) return AT_OK;
 	if (!q_blob || !q_off || !q_len || !out_target || !out_score || !out_end_i || !out_end_j || !out_state || !out_nhits ||
-	    (nt > 0 && (!t_blob || !t_off || !t_len)))
+	    (rev && !out_strand) || (nt > 0 && (!t_blob || !t_off || !t_len)))
 		return fail(h, AT_ERR_ARG, "at_search: NULL argument");
 	const bool need_base = mode == AT_MODE_LOCAL || mode == AT_MODE_OVERLAP;   /* (as upload_reads) */
 	for (int64_t q = 0; q < nq; ++q) {
@@ -2140,8 +2175,9 @@ extern "C" int at_search(at_handle *h, int mode,
 	}
 	return guarded(h, "at_search", [&]() -> int {
 		for (int64_t e = 0; e < nq * k; ++e) { out_target[e] = -1; out_score[e] = 0; out_end_i[e] = 0; out_end_j[e] = 0; out_state[e] = 0; }
+		if (out_strand) for (int64_t e = 0; e < nq * k; ++e) out_strand[e] = -1;
 		for (int64_t q = 0; q < nq; ++q) out_nhits[q] = 0;
-		if (nt == 0) { snprintf(h->cfg, sizeof h->cfg, "search: 0 blocks, 0 slices, k=%d; ", k); return (int)AT_OK; }
+		if (nt == 0) { snprintf(h->cfg, sizeof h->cfg, "search: 0 blocks, 0 slices, k=%d%s; ", k, strands_text(strands)); return (int)AT_OK; }
 		/* one read set: the queries' and the targets' bytes side by side (a copy of the input, small beside the sweep) */
 		int64_t bytes = 0;
 		for (int64_t q = 0; q < nq; ++q) bytes += q_len[q];
@@ -2157,10 +2193,49 @@ extern "C" int at_search(at_handle *h, int mode,
 			off[(size_t)r] = at; len[(size_t)r] = l; at += l;
 		}
 		ReadSet rs;
-		int rc = upload_reads(h, mode, nq + nt, blob.data(), off.data(), len.data(), &rs);
+		int rc = upload_reads(h, mode, nq + nt, blob.data(), off.data(), len.data(), &rs, rev ? nq : 0);
 		if (rc) return rc;
-		return search_lists(h, mode, nq, q_len, nt, t_len, rs, k, use_cutoff, cutoff, out_target, out_score, out_end_i, out_end_j, out_state, out_nhits);
+		return search_lists(h, mode, nq, q_len, nt, t_len, rs, k, use_cutoff, cutoff, strands, out_target, out_score, out_end_i, out_end_j,
+		                    out_state, out_strand, out_nhits);
 	});
+}
+
+extern "C" int at_search(at_handle *h, int mode,
+                         int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+                         int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+                         int k, int use_cutoff, int32_t cutoff,
+                         int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
+                         int32_t *out_state, int32_t *out_nhits)
+{
+	return at_search_strands(h, mode, nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len, k, use_cutoff, cutoff, AT_STRAND_FWD,
+	                         out_target, out_score, out_end_i, out_end_j, out_state, nullptr, out_nhits);
+}
+
+/* ---- reverse complement: the host helper and the device entry (the kernel: at_revcomp.hip) ---- */
+extern "C" int at_revcomp(const uint8_t *s, int32_t len, uint8_t *out)
+{
+	static constexpr at::CompTable comp = at::make_comp_table();
+	if (len < 0 || (len > 0 && (!s || !out))) return fail(nullptr, AT_ERR_ARG, "at_revcomp: NULL argument or negative length");
+	for (int32_t x = 0; x < len; ++x) out[x] = comp.t[s[len - 1 - x]];
+	return AT_OK;
+}
+
+extern "C" int at_revcomp_device(at_handle *h, int64_t nseq, const uint32_t *d_seq, int bits,
+                                 const int64_t *d_woff, const int32_t *d_len,
+                                 uint32_t *d_out, const int64_t *d_out_woff, void *stream)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_revcomp_device: NULL handle");
+	if (nseq < 0) return fail(h, AT_ERR_ARG, "negative nseq");
+	if (bits != 2 && bits != 8) return fail(h, AT_ERR_ARG, "bits must be 2 or 8");
+	if (nseq == 0) return AT_OK;
+	if (!d_seq || !d_woff || !d_len || !d_out) return fail(h, AT_ERR_ARG, "NULL device pointer");
+	HIP_TRY(h, hipSetDevice(h->device));
+	drop_stale_error();
+	at::RevcompArgs ra;
+	ra.nseq = nseq; ra.seq = d_seq; ra.woff = (const long long *)d_woff; ra.len = d_len;
+	ra.out = d_out; ra.out_woff = (const long long *)(d_out_woff ? d_out_woff : d_woff);
+	HIP_TRY(h, at_revcomp_launch(&ra, bits, h->ncu, (hipStream_t)stream));
+	return AT_OK;
 }
 
 namespace {

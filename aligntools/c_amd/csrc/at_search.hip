@@ -11,7 +11,8 @@ __global__ __launch_bounds__(256) void at_search_desc_k(const SearchDescArgs a)
 	for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < a.n; p += stride) {
 		const long long x = a.s0 + p;
 		const long long qi = x / a.ntb, ti = x - qi * a.ntb;
-		const int q = a.qperm[a.qa + qi], t = a.nq + a.tperm[a.ta + ti];
+		const int e = a.qperm[a.qa + qi], t = a.nq + a.tperm[a.ta + ti];
+		const int q = a.enc ? ((e & 1) ? a.nrev0 + (e >> 1) : e >> 1) : e;
 		a.woff1[p] = a.swoff[q]; a.len1[p] = a.slen[q];
 		a.woff2[p] = a.swoff[t]; a.len2[p] = a.slen[t];
 	}
@@ -25,8 +26,9 @@ __device__ __forceinline__ void search_cx(unsigned long long &key, int &ei, int 
 	if (hi ? ok > key : ok < key) { key = ok; ei = oei; ej = oej; st = ost; }
 }
 
-/* Four wavefronts per workgroup, one query each.  The query's candidates in the slice are one contiguous run of pairs; they are
- * taken 64 at a time (one per lane).  A batch none of whose keys beats the list's K-th entry is skipped (one ballot: the common
+/* Four wavefronts per workgroup, one caller query each.  The query's candidates in the slice are one contiguous run of pairs (with
+ * both strands: the run of its two adjacent entries, so no other wavefront touches its list); they are taken 64 at a time (one per
+ * lane).  A batch none of whose keys beats the list's K-th entry is skipped (one ballot: the common
  * case once the list has filled); otherwise the batch is sorted descending across the wave (bitonic, __shfl_xor), reversed against
  * the list (lane i: the larger of list[i] and batch[63 - i], a bitonic sequence holding the top 64 of both) and merged (bitonic). */
 __global__ __launch_bounds__(256) void at_search_merge_k(const SearchMergeArgs a)
@@ -34,10 +36,11 @@ __global__ __launch_bounds__(256) void at_search_merge_k(const SearchMergeArgs a
 	const int lane = threadIdx.x & 63;
 	const int w = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
 	if (w >= a.nqs) return;                                   /* (wave-uniform) */
-	const long long qi = a.s0 / a.ntb + w;                    /* the query's index in the block */
-	const int q = a.qperm[a.qa + qi];
-	const long long lo = qi * a.ntb > a.s0 ? qi * a.ntb : a.s0;
-	const long long hi_ = (qi + 1) * a.ntb < a.s0 + a.n ? (qi + 1) * a.ntb : a.s0 + a.n;
+	const long long gs = a.ntb << a.two;                      /* pairs of one caller query in the block */
+	const long long g = a.s0 / gs + w;                        /* the caller query's index in the block */
+	const int q = a.qperm[a.qa + (g << a.two)] >> a.enc;
+	const long long lo = g * gs > a.s0 ? g * gs : a.s0;
+	const long long hi_ = (g + 1) * gs < a.s0 + a.n ? (g + 1) * gs : a.s0 + a.n;
 	const size_t base = (size_t)q * a.k;
 	unsigned long long key = 0;
 	int ei = 0, ej = 0, st = 0;
@@ -54,7 +57,9 @@ __global__ __launch_bounds__(256) void at_search_merge_k(const SearchMergeArgs a
 			if (s == INT32_MIN) bad = 1;
 			else if (!a.use_cutoff || (a.is_edit ? s <= a.cutoff : s >= a.cutoff)) {
 				const unsigned r = (unsigned)(a.is_edit ? -s : s) ^ 0x80000000u;   /* larger = better */
-				const unsigned t = (unsigned)a.tperm[a.ta + (c - qi * a.ntb)];
+				const long long qi = (g << a.two) + (c - g * gs >= a.ntb);         /* the entry (query, strand) of the block */
+				unsigned t = (unsigned)a.tperm[a.ta + (c - qi * a.ntb)];
+				if (a.enc) t = (t << 1) | ((unsigned)a.qperm[a.qa + qi] & 1u);
 				ck = ((unsigned long long)r << 32) | (unsigned long long)(~t);
 				cei = a.end_i[p]; cej = a.end_j[p]; cst = a.state[p];
 			}

@@ -11,6 +11,12 @@
  * A hit is a 64-bit key: the rank-ordered score in the high word (higher = better), the inverted caller index of the target in the
  * low word (smaller index = better), so one unsigned compare is the whole ranking rule and no two real keys are equal; 0 = empty.
  * The merged list is the top K of a total order over everything seen, so it does not depend on how the block was sliced.
+ *
+ * Strands (at_search_strands): with a reverse strand (`enc`) an entry of qperm is (caller query << 1) | strand, strand 1 being the
+ * read nrev0 + query of the read set (its reverse complement, at_revcomp.hip), and the low word of a key is the inverted
+ * (target << 1) | strand: after the target index, strand 0 ranks before strand 1.  With both strands (`two`) the two entries of a
+ * query are adjacent in the block's order, strand 0 first, so the candidates of a caller query are still ONE contiguous run of
+ * the block (2 ntb pairs) and one wavefront of the merge kernel owns the query's list, whichever strand a candidate is of.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +29,8 @@ struct SearchDescArgs {
 	long long ntb;                 /* targets in the block */
 	int qa, ta;                    /* the block's first query / target in the sorted orders */
 	int nq;                        /* targets are reads nq .. of the read set */
+	int enc;                       /* 0: qperm holds caller queries; 1: (query << 1) | strand */
+	int nrev0;                     /* enc: the reverse complement of query q is read nrev0 + q */
 	const int *qperm, *tperm;      /* sorted position -> caller index */
 	const long long *swoff;        /* the read set's word offsets and lengths */
 	const int *slen;
@@ -33,7 +41,8 @@ struct SearchDescArgs {
 struct SearchMergeArgs {
 	long long s0, n, ntb;
 	int qa, ta;
-	int nqs;                       /* queries with candidates in the slice; the first is q0 = s0 / ntb of the block */
+	int enc, two;                  /* enc as above; two: a caller query has two adjacent entries (both strands), else one */
+	int nqs;                       /* caller queries with candidates in the slice; the first is s0 / (ntb << two) of the block */
 	const int *qperm, *tperm;
 	const int *score, *end_i, *end_j, *state;   /* the slice's results, indexed by pair - s0 */
 	int k;                         /* 1 .. 64 */

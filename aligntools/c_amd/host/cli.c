@@ -7,7 +7,7 @@
  * Extension (absent from the reference, does not change the five commands):
  *   alignTools batch <command> [options] <pairs.fa>
  *     records (2k, 2k+1) of the file form pair k; all pairs go to the GPU in one batch.
- *   alignTools batch <command> [options] --queries <queries.fa> [--best K] <targets.fa>
+ *   alignTools batch <command> [options] --queries <queries.fa> [--best K] [--both-strands] <targets.fa>
  *     every query against every target; the best K hits of each query are printed.
  */
 #define _POSIX_C_SOURCE 200809L
@@ -134,6 +134,9 @@ static int main_single(int cmd, int argc, char *argv[])
  *                    earlier target -- each printed as a pair line of this command (at_search; strings from at_align_batch_strings
  *                    on the hit pairs).  --min-score T (not for edit) keeps hits that score at least T.  fit: targets shorter than
  *                    a query are not its hits; -s takes the site list from the first target's comment.  One GPU.
+ *                    --both-strands also searches every query's reverse complement (at_search_strands; made on the GPU): a hit's
+ *                    header line gets a fourth column, + or -, and the strings of a - hit are those of the reverse-complemented
+ *                    query; ties on score and target: + first.
  *     --gpus N       one process per GPU: this process starts N workers (itself, with AT_RANK / AT_WORLD / AT_DEVICE /
  *                    AT_COMM_DIR in their environment), rank 0's options are broadcast over RCCL, every rank aligns a
  *                    contiguous share of the pairs on its own GPU, results are gathered over RCCL and rank 0 prints them
@@ -142,7 +145,7 @@ static int main_single(int cmd, int argc, char *argv[])
  * thread -- which also pays the HIP start-up, in the shadow of the first chunks' parsing -- sends each chunk to the GPU
  * and writes its results with one fwrite.  Memory is bounded by the chunks in flight, whatever the size of the file;
  * --all-vs-all keeps the read set and streams slices of the triangle instead (at_align_allpairs_stream). */
-typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set; } batch_flags;
+typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both; } batch_flags;
 
 /* linear index p of the strict upper triangle of n x n (row-major) -> (a, b), a < b: closed form + integer correction */
 static void tri_seek(int64_t p, int64_t n, int64_t *a, int64_t *b)
@@ -180,19 +183,24 @@ static void tb_score(tbuf *t, int32_t v, int is_edit)
 	while (n) t->s[t->l++] = d[--n];
 	if (!is_edit) { memcpy(t->s + t->l, ".000000", 7); t->l += 7; }
 }
-/* "<name1>\t<name2>\t<score>\n[<r1>\n<r2>\n]" */
-static void tb_pair(tbuf *t, const char *na, const char *nb, int32_t score, int is_edit, const char *r1, const char *r2, size_t rl)
+/* "<name1>\t<name2>\t<score>[\t<strand>]\n[<r1>\n<r2>\n]" (strand: '+' / '-', 0 = no such column) */
+static void tb_pair_strand(tbuf *t, const char *na, const char *nb, int32_t score, int is_edit, char strand, const char *r1, const char *r2, size_t rl)
 {
 	const size_t la = strlen(na), lb = strlen(nb);
 	tb_need(t, la + lb + 2 * rl + 64);
 	memcpy(t->s + t->l, na, la); t->l += la; t->s[t->l++] = '\t';
 	memcpy(t->s + t->l, nb, lb); t->l += lb; t->s[t->l++] = '\t';
 	tb_score(t, score, is_edit);
+	if (strand) { t->s[t->l++] = '\t'; t->s[t->l++] = strand; }
 	t->s[t->l++] = '\n';
 	if (r1) {
 		memcpy(t->s + t->l, r1, rl); t->l += rl; t->s[t->l++] = '\n';
 		memcpy(t->s + t->l, r2, rl); t->l += rl; t->s[t->l++] = '\n';
 	}
+}
+static void tb_pair(tbuf *t, const char *na, const char *nb, int32_t score, int is_edit, const char *r1, const char *r2, size_t rl)
+{
+	tb_pair_strand(t, na, nb, score, is_edit, 0, r1, r2, rl);
 }
 static void tb_flush(tbuf *t)
 {
@@ -584,8 +592,9 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	at_handle *h;
 	slice_t w;
 	tbuf out = {NULL, 0, 0};
-	int64_t nq, nt, q, x, nhit = 0, *qoff, *toff;
-	int32_t *qlen, *tlen, *tgt, *sc, *ei, *ej, *st, *nh;
+	int64_t nq, nt, q, x, nhit = 0, *qoff, *toff, *roff = NULL;
+	int32_t *qlen, *tlen, *tgt, *sc, *ei, *ej, *st, *nh, *sd = NULL;
+	uint8_t *blob2 = NULL;
 	int rc, j;
 	const int tb = !bf->score_only && cmd != C_EDIT, kb = bf->best;
 	const int mode = cmd == C_GLOBAL ? AT_MODE_GLOBAL : cmd == C_LOCAL ? AT_MODE_LOCAL : cmd == C_FIT ? AT_MODE_FIT
@@ -616,30 +625,59 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	ei = (int32_t *)at_xmalloc((size_t)nq * kb * 4); ej = (int32_t *)at_xmalloc((size_t)nq * kb * 4);
 	st = (int32_t *)at_xmalloc((size_t)nq * kb * 4); nh = (int32_t *)at_xmalloc((size_t)nq * 4);
 	trace("search: records read, queries", nq);
-	rc = at_search(h, mode, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, bf->min_on, bf->min_score, tgt, sc, ei, ej, st, nh);
+	if (bf->both) {
+		sd = (int32_t *)at_xmalloc((size_t)nq * kb * 4);
+		rc = at_search_strands(h, mode, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, bf->min_on, bf->min_score, AT_STRAND_BOTH,
+		                       tgt, sc, ei, ej, st, sd, nh);
+	} else
+		rc = at_search(h, mode, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, bf->min_on, bf->min_score, tgt, sc, ei, ej, st, nh);
 	if (rc != AT_OK) die("%s", at_last_error(h));
 	trace("search: done, queries", nq);
 	for (q = 0; q < nq; ++q) nhit += nh[q];
 	if (tb && nhit > 0) {
+		const uint8_t *blob = c.blob;
 		slice_reserve(&w, nhit);
+		if (bf->both) {
+			/* the strings of a - hit are those of the reverse-complemented query: a second blob, the records and behind them the
+			 * reverse complement (at_revcomp) of every query that has such a hit */
+			int64_t end = 0, at;
+			roff = (int64_t *)at_xmalloc((size_t)nq * 8);
+			for (x = 0; x < nq + nt; ++x) if ((int64_t)(c.off[x] + c.len[x]) > end) end = (int64_t)(c.off[x] + c.len[x]);
+			at = end;
+			for (q = 0; q < nq; ++q) {
+				roff[q] = -1;
+				for (j = 0; j < nh[q]; ++j) if (sd[q * kb + j] == 1) roff[q] = at;
+				if (roff[q] >= 0) at += qlen[q];
+			}
+			if (at > end) {
+				blob2 = (uint8_t *)at_xmalloc((size_t)at + 64);
+				memcpy(blob2, c.blob, (size_t)end);
+				memset(blob2 + at, 0, 64);
+				for (q = 0; q < nq; ++q)
+					if (roff[q] >= 0 && at_revcomp(c.blob + qoff[q], qlen[q], blob2 + roff[q]) != AT_OK) die("%s", at_last_error(NULL));
+				blob = blob2;
+			}
+		}
 		x = 0;
 		for (q = 0; q < nq; ++q)
 			for (j = 0; j < nh[q]; ++j, ++x) {
 				const int64_t t = nq + tgt[q * kb + j];
-				w.off1[x] = qoff[q]; w.l1[x] = qlen[q]; w.off2[x] = (int64_t)c.off[t]; w.l2[x] = (int32_t)c.len[t];
+				w.off1[x] = sd && sd[q * kb + j] == 1 ? roff[q] : qoff[q];
+				w.l1[x] = qlen[q]; w.off2[x] = (int64_t)c.off[t]; w.l2[x] = (int32_t)c.len[t];
 			}
-		slice_run(&w, h, cmd, 1, c.blob, nhit);
+		slice_run(&w, h, cmd, 1, blob, nhit);
 		trace("search: hit strings rendered, hits", nhit);
 	}
 	x = 0;
 	for (q = 0; q < nq; ++q) {
 		for (j = 0; j < nh[q]; ++j, ++x)
-			tb_pair(&out, c.names + c.name_off[q], c.names + c.name_off[nq + tgt[q * kb + j]], sc[q * kb + j], cmd == C_EDIT,
-			        tb ? w.r1 + w.slot[x] : NULL, tb ? w.r2 + w.slot[x] : NULL, tb ? (size_t)w.nops[x] : 0);
+			tb_pair_strand(&out, c.names + c.name_off[q], c.names + c.name_off[nq + tgt[q * kb + j]], sc[q * kb + j], cmd == C_EDIT,
+			        sd ? (sd[q * kb + j] == 1 ? '-' : '+') : 0, tb ? w.r1 + w.slot[x] : NULL, tb ? w.r2 + w.slot[x] : NULL, tb ? (size_t)w.nops[x] : 0);
 		if (out.l > ((size_t)8 << 20)) tb_flush(&out);
 	}
 	tb_flush(&out);
 	free(out.s); free(qoff); free(qlen); free(toff); free(tlen); free(tgt); free(sc); free(ei); free(ej); free(st); free(nh);
+	free(sd); free(roff); free(blob2);
 	slice_free(&w);
 	at_chunk_free(&c);
 	return 0;
@@ -704,10 +742,10 @@ static int main_batch(int argc, char *argv[], char *argv0)
 {
 	int cmd = -1, k, n = 0;
 	opt_t *opt = init_opt();
-	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0};
+	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0};
 	char **av = (char **)at_xmalloc((size_t)(argc + 1) * sizeof(char *));
 	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] <pairs.fa>\n"
-	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--min-score T] [--score-only] <targets.fa>\n";
+	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] <targets.fa>\n";
 	/* the long flags of the extension are taken out before getopt sees the reference's short options */
 	for (k = 0; k < argc; ++k) {
 		if (strcmp(argv[k], "--score-only") == 0) bf.score_only = 1;
@@ -716,6 +754,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (strcmp(argv[k], "--min-score") == 0 && k + 1 < argc) { bf.min_on = 1; bf.min_score = atoi(argv[++k]); }
 		else if (strcmp(argv[k], "--queries") == 0 && k + 1 < argc) bf.queries = argv[++k];
 		else if (strcmp(argv[k], "--best") == 0 && k + 1 < argc) { bf.best = atoi(argv[++k]); bf.best_set = 1; }
+		else if (strcmp(argv[k], "--both-strands") == 0) bf.both = 1;
 		else av[n++] = argv[k];
 	}
 	av[n] = NULL;
@@ -729,6 +768,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (bf.queries && bf.gpus > 1) why = "--queries runs on one GPU: it does not go with --gpus N > 1";
 		else if (bf.queries && bf.min_on && cmd == C_EDIT) why = "--min-score does not go with `batch edit --queries` (edit ranks by distance)";
 		else if (bf.best_set && !bf.queries) why = "--best goes with --queries";
+		else if (bf.both && !bf.queries) why = "--both-strands goes with --queries";
 		else if (bf.queries && (bf.best < 1 || bf.best > 64)) why = "--best K needs 1 <= K <= 64";
 		if (why) { fprintf(stderr, "%s\n%s", why, usage_line); free(opt); free(av); return 1; }
 	}

@@ -205,6 +205,47 @@ int at_search(at_handle *h, int mode,
               int32_t *out_state, int32_t *out_nhits);
 
 /*
+ * Reverse complement.  The complement of a byte is stated once, here, as (from, to) pairs of upper-case letters -- the IUPAC
+ * nucleotide codes, U read as T -- and holds for the lower-case letters likewise; S, W, N and every other byte value map to
+ * themselves.  The host helper and the device kernel (csrc/at_revcomp.hip) build their 256-entry table from this string.
+ */
+#define AT_COMPLEMENT_PAIRS "ATTACGGCUARYYRKMMKBVVBDHHD"
+/* Host helper: out[0..len) = the reverse complement of s[0..len) under the table above; out may not alias s. */
+int at_revcomp(const uint8_t *s, int32_t len, uint8_t *out);
+/*
+ * The same for `nseq` PACKED reads already in device memory (the word layout of at_align_batch_device, bits = 2 or 8): for r in
+ * [0, nseq) the words of the reverse complement of the read at d_seq + d_woff[r] (d_len[r] bases) are written to
+ * d_out + d_out_woff[r]; d_out_woff == NULL: the same offsets as d_woff.  Bit for bit what at_pack_batch gives for the
+ * reverse-complemented bytes: ceil(len / bases per word) words and the zero slack word behind them, zero bits behind the last
+ * base; no other word of d_out is written.  d_out must not overlap d_seq.  Asynchronous on `stream`; the same handle / stream
+ * rules as at_align_batch_device.
+ */
+int at_revcomp_device(at_handle *h, int64_t nseq, const uint32_t *d_seq, int bits,
+                      const int64_t *d_woff, const int32_t *d_len,
+                      uint32_t *d_out, const int64_t *d_out_woff, void *stream);
+
+/*
+ * at_search on one or both strands of the queries.  strands = AT_STRAND_FWD: at_search itself (out_strand may be NULL);
+ * AT_STRAND_REV: every query is searched as its reverse complement; AT_STRAND_BOTH: as given and as its reverse complement.
+ *   a hit is (target, strand): out_strand[e] is 0 for the query as given, 1 for its reverse complement, -1 for an unused entry
+ *   score / end_i / end_j / state of a strand-1 hit are exactly what at_align_batch returns for the pair (reverse complement of
+ *   the query under at_revcomp, target): end_i counts along the reverse-complemented query.  Targets are never complemented,
+ *   so a fit -s site list keeps its meaning
+ *   rank: better score first, ties to the smaller target index, then strand 0 before strand 1; a query equal to its own
+ *   reverse complement yields two hits per target, adjacent in its list
+ * The queries go up once, as given; the reverse strand is made on the device from the packed words (at_revcomp_device's
+ * kernel).  With a reverse strand the call needs nt < 2^30 and 2 nq + nt < 2^31 (AT_ERR_ARG beyond).  at_last_config reads
+ * "search: B blocks, S slices, k=K, strands=rev; " or "... k=K, strands=both; " and the first slice's sweep.
+ */
+enum { AT_STRAND_FWD = 1, AT_STRAND_REV = 2, AT_STRAND_BOTH = 3 };
+int at_search_strands(at_handle *h, int mode,
+                      int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+                      int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+                      int k, int use_cutoff, int32_t cutoff, int strands,
+                      int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
+                      int32_t *out_state, int32_t *out_strand, int32_t *out_nhits);
+
+/*
  * Output rendering on the GPU: what trace_back_* + strrev produce (alignment.h:372-412,
  * 558-592, 766-800, 896-922, 172-184) -- the two gapped strings, in reading order -- from the op codes and end
  * cells at_align_batch_device left in HBM and the same packed sequences.  Pair k's strings are written to

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """search_rate.py -- rates of the query-vs-target search (at_search) on one GPU; one JSON line per measurement.
 
-    python3 tools/search_rate.py [--cases abc] [--reps 3] [--out FILE]
+    python3 tools/search_rate.py [--cases abcs] [--reps 3] [--out FILE] [--parent-lib LIB]
 
   a  local 150 x 150, 20 000 queries x 500 targets (10 M pairs, k = 1): at_search end to end (host sequences in, nq x k hits
      out) against at_align_batch_device on the same 10 M pairs as one uniform device-resident batch, scores only -- the two
@@ -9,7 +9,12 @@
   b  fit -s, 10 000 reads of 150 x 200 windows of 500 (k = 1)
   c  `alignTools batch local --queries q.fa t.fa` against `batch local --score-only` on the equivalent pair file (1 000 x 200):
      wall clock and output bytes
-Kernel shares: run case a alone under `rocprofv3 --kernel-trace --stats` (tools/README.md).
+  s  both strands, the shape of case a (20 000 queries x 500 targets, k = 1: 20 M pairs): at_search_strands(BOTH) against what a
+     caller had to do before it existed -- reverse-complement every query on the host, at_search on the 40 000 queries, merge the
+     two hit lists per query -- with that at_search taken from --parent-lib (a build of the commit before at_search_strands; the
+     same library when the option is absent).  The two alternate, `reps` times each after a warm-up; the host's time for the
+     reverse complements and for the merge is reported separately.  `--cases S`: the both-strand search alone (for a kernel trace)
+Kernel shares: run case a (or S) alone under `rocprofv3 --kernel-trace --stats` (tools/README.md).
 """
 import argparse
 import ctypes as C
@@ -115,6 +120,106 @@ def case_a(al, reps, out):
                    search_config=al.last_config, device_batch_config=dev_cfg))
 
 
+COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+class ParentSearch(Search):
+    """at_search of another build of the library (its own handle), loaded beside this one."""
+
+    class _Al:
+        pass
+
+    def __init__(self, path, queries, targets):
+        lib = C.CDLL(path)
+        lib.at_init.restype = C.c_int
+        lib.at_init.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
+        lib.at_last_error.restype = C.c_char_p
+        lib.at_last_error.argtypes = [C.c_void_p]
+        lib.at_last_config.restype = C.c_char_p
+        lib.at_last_config.argtypes = [C.c_void_p]
+        lib.at_set_scoring.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_int), C.c_int]
+        lib.at_search.restype = C.c_int
+        lib.at_search.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_int, C.c_int32] + [C.c_void_p] * 6
+        h = C.c_void_p()
+        dev = (C.c_int * 1)(0)
+        assert lib.at_init(dev, 1, C.byref(h)) == 0, lib.at_last_error(None)
+        assert lib.at_set_scoring(h, 1, -2, -5, -1, -10, 0, (C.c_int * 1)(0), 0) == 0
+        al = self._Al()
+        al._lib, al._h = lib, h
+
+        def check(rc):
+            assert rc == 0, lib.at_last_error(h)
+        al._check = check
+        self.lib = lib
+        super().__init__(al, queries, targets)
+
+
+def strands_run(s, mode, k=1):
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    outs = [np.zeros(s.nq * k, dtype=np.int32) for _ in range(6)] + [np.zeros(s.nq, dtype=np.int32)]
+    t0 = time.perf_counter()
+    s.al._check(s.al._lib.at_search_strands(s.al._h, mode, s.nq, p(s.q[0]), p(s.q[1]), p(s.q[2]), s.nt, p(s.t[0]), p(s.t[1]), p(s.t[2]),
+                                            k, 0, 0, A.STRAND_BOTH, *[p(o) for o in outs]))
+    return time.perf_counter() - t0, outs
+
+
+def case_s(al, reps, out, parent_lib, alone=False):
+    rng = np.random.default_rng(4)
+    nq, nt, L = 20000, 500, 150
+    _, qs = reads(rng, nq, L)
+    _, ts = reads(rng, nt, L)
+    for t in range(0, nt, 2):                                               # half of the targets hold a stretch of a query, every
+        q = qs[int(rng.integers(nq))]                                       # second one of its reverse complement
+        if t & 2:
+            q = q.translate(COMPLEMENT)[::-1]
+        ts[t] = ts[t][:40] + q[40:120] + ts[t][120:]
+    al.set_scoring(1, -2, -5, -1, -10)
+    both = Search(al, qs, ts)
+    cells = 2.0 * nq * nt * L * L
+    if alone:
+        strands_run(both, A.MODE_LOCAL)
+        times = [strands_run(both, A.MODE_LOCAL)[0] for _ in range(reps)]
+        emit(out, dict(case="S", what="local 150x150, 20000 queries x 500 targets, both strands, k=1", pairs=2 * nq * nt, reps=reps,
+                       strands_s=[round(x, 4) for x in times], strands_gcups=round(cells / min(times) / 1e9, 1), strands_config=al.last_config))
+        return
+
+    def by_hand(first=False):
+        """What a caller does without at_search_strands.  The first call also builds the parent's handle and arrays."""
+        t0 = time.perf_counter()
+        rc = [q.translate(COMPLEMENT)[::-1] for q in qs]
+        t_rc = time.perf_counter() - t0
+        if first:
+            by_hand.s = ParentSearch(parent_lib, qs + rc, ts) if parent_lib else Search(al, qs + rc, ts)
+        t_search, o = by_hand.s.run(A.MODE_LOCAL)                           # (its host arrays were built once, as `both`'s)
+        t0 = time.perf_counter()
+        f, r = slice(0, nq), slice(nq, 2 * nq)
+        take_r = o[1][r] > o[1][f]                                          # ties: target index, then the query as given
+        take_r |= (o[1][r] == o[1][f]) & (o[0][r] < o[0][f])
+        merged = [np.where(take_r, x[r], x[f]) for x in o[:5]] + [take_r.astype(np.int32)]
+        t_merge = time.perf_counter() - t0
+        return t_rc, t_search, t_merge, merged
+    by_hand(first=True)
+    strands_run(both, A.MODE_LOCAL)                                         # warm-up of both
+    ta, tb = [], []
+    for _ in range(reps):
+        tb.append(by_hand()[:3])
+        dt, outs = strands_run(both, A.MODE_LOCAL)
+        ta.append(dt)
+    merged = by_hand()[3]
+    for name, x, y in zip(("target", "score", "end_i", "end_j", "state", "strand"), outs, merged):
+        assert (x == y).all(), "both-strand search differs from the merged one-strand searches in " + name
+    e2e = [sum(x) for x in tb]
+    emit(out, dict(case="s", what="local 150x150, 20000 queries x 500 targets, both strands, k=1", pairs=2 * nq * nt, reps=reps,
+                   parent_lib=os.path.basename(parent_lib) if parent_lib else None,
+                   strands_s=[round(x, 4) for x in ta],
+                   by_hand_s=[round(x, 4) for x in e2e], by_hand_revcomp_s=[round(x[0], 4) for x in tb],
+                   by_hand_search_s=[round(x[1], 4) for x in tb], by_hand_merge_s=[round(x[2], 4) for x in tb],
+                   strands_gcups=round(cells / min(ta) / 1e9, 1), by_hand_gcups=round(cells / min(e2e) / 1e9, 1),
+                   by_hand_search_gcups=round(cells / min(x[1] for x in tb) / 1e9, 1),
+                   strand1_hits=int(outs[5].sum()), strands_config=al.last_config))
+
+
 def case_b(al, reps, out):
     rng = np.random.default_rng(2)
     _, qs = reads(rng, 10000, 150)
@@ -162,14 +267,19 @@ def main():
     ap.add_argument("--cases", default="abc")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--parent-lib", default=None, help="case s: a libaligntools_hip.so of the commit before at_search_strands")
     a = ap.parse_args()
-    al = A.Aligner(0) if ("a" in a.cases or "b" in a.cases) else None
+    al = A.Aligner(0) if set(a.cases) & set("abSs") else None
     if "a" in a.cases:
         case_a(al, a.reps, a.out)
     if "b" in a.cases:
         case_b(al, a.reps, a.out)
     if "c" in a.cases:
         case_c(a.reps, a.out)
+    if "s" in a.cases:
+        case_s(al, a.reps, a.out, a.parent_lib)
+    if "S" in a.cases:
+        case_s(al, a.reps, a.out, None, alone=True)
 
 
 if __name__ == "__main__":
