@@ -202,9 +202,15 @@ static int do_fit(const char *s1, int l1, const char *s2, int l2, const ato_scor
 {
 	mats W; int i, j, st, rc, jmax = -1, state = 0, sj = sc->use_jump;
 	double m = sc->m, u = sc->u, o = sc->o, e = sc->e, g = sc->j, c[4], best = NEG;
+	unsigned char *listed = NULL;            /* listed[j] = site_listed(j, ...): one scan of the list per column, not per cell */
 	if (l1 > l2) return -1;                  /* reference die()s :599 */
 	if (l1 < 1) return -2;
 	if (mats_new(&W, l1, l2, 1)) { mats_free(&W); return -1; }
+	if (sj) {
+		listed = malloc((size_t)l2 + 1);
+		if (!listed) { mats_free(&W); return -1; }
+		for (j = 0; j <= l2; ++j) listed[j] = (unsigned char)site_listed(j, sc->sites, sc->nsites);
+	}
 	/* column 0 first, then row 0 overrides (0,0)  :612-624 */
 	for (i = 0; i <= l1; ++i) { AT(W.M, i, 0) = NEG; AT(W.U, i, 0) = NEG; AT(W.L, i, 0) = NEG; AT(W.J, i, 0) = NEG; }
 	for (j = 0; j <= l2; ++j) { AT(W.M, 0, j) = 0.0; AT(W.U, 0, j) = 0.0; AT(W.J, 0, j) = NEG; AT(W.L, 0, j) = NEG; }
@@ -225,7 +231,7 @@ static int do_fit(const char *s1, int l1, const char *s2, int l2, const ato_scor
 				/* :658-666.  isvalueinarray returns the enum `true`(0) when FOUND,
 				 * and the caller tests C truthiness, so the M->J opening is
 				 * allowed exactly when (j-1) is NOT a listed site. */
-				if (!site_listed(j - 1, sc->sites, sc->nsites)) {
+				if (!listed[j - 1]) {
 					c[0] = AT(W.M, i, j - 1) + g; c[1] = AT(W.J, i, j - 1);
 					st = first_max(&AT(W.J, i, j), c, 2);
 					if (st >= 0) AT(W.pJ, i, j) = (unsigned char)(st == 0 ? P_MID : P_JUMP);
@@ -241,6 +247,7 @@ static int do_fit(const char *s1, int l1, const char *s2, int l2, const ato_scor
 		if (best < AT(W.M, l1, j)) { best = AT(W.M, l1, j); jmax = j; state = P_MID; }
 	for (j = 0; j < l2; ++j)
 		if (best < AT(W.L, l1, j)) { best = AT(W.L, l1, j); jmax = j; state = P_LOW; }
+	free(listed);
 	if (!state) { mats_free(&W); return -2; }
 	*score = best; *ei = l1; *ej = jmax; *est = state == P_MID ? ATO_ST_MID : ATO_ST_LOW;
 	rc = walk_affine(&W, l1, jmax, state, 0, b, &i, &j);       /* :558-592, while(i>0) */

@@ -20,6 +20,9 @@ Files written
     known_answers_big.jsonl   the two runs of the reference's own fixtures that need gigabytes in the reference
                           (`fit -s test/tmp.fa`, 1 327 x 114 491: 7.3 GB; `global test/test_fit.fa`,
                           257 x 33 733); written by `python oracle/make_golden.py --only big` (the default run leaves it alone)
+    dense_sites.jsonl     fit -s under dense site lists (every column listed but a few at the mask's word edges; the generator of
+                          tests/test_dense_sites.py): six lists x 32 pairs of 60 x 140, two lists x 8 pairs of 150 x 500; written by
+                          `python oracle/make_golden.py --only dense` (the default run leaves it alone)
 """
 import hashlib
 import json
@@ -54,13 +57,13 @@ def md5(s):
     return hashlib.md5(s.encode("latin1")).hexdigest()
 
 
-def case(mode, s1, s2, m, u, o, e, j=-10, use_jump=False, sites=None, tag="", keep_inputs=True):
+def case(mode, s1, s2, m, u, o, e, j=-10, use_jump=False, sites=None, tag="", keep_inputs=True, long=LONG):
     r = O.ref_align(O.MODE_NAMES[mode], s1, s2, m, u, o, e, j, use_jump, sites)
     assert r["rc"] == 0, (mode, len(s1), len(s2))
     d = dict(mode=mode, m=m, u=u, o=o, e=e, j=j, use_jump=bool(use_jump), sites=list(sites or []),
              s1=s1, s2=s2, score=r["score"], tag=tag)
     if mode != "edit":
-        if len(r["r1"]) > LONG:
+        if len(r["r1"]) > long:
             d["rlen"] = len(r["r1"])
             d["r1_md5"] = md5(r["r1"])
             d["r2_md5"] = md5(r["r2"])
@@ -227,6 +230,26 @@ def random_dna(rng):
     return out
 
 
+def dense_sites():
+    """fit -s with everything listed except a few allowed columns, spliced reads ending at or next to them.  Each list differs: the
+    allowed columns of tests/test_dense_sites.py shifted by 0 .. 5 (other bits of the mask's words), each with its own scoring.
+    (The batches come from that module's dense_batch / _pair: a change there changes what a later regeneration writes, not the
+    committed file, which holds its own inputs and the reference's outputs.)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_dense_sites as D
+    out = []
+    for l1, l2, lists, n in ((60, 140, 6, 32), (150, 500, 2, 8)):
+        for k in range(lists):
+            rng = random.Random(1000 * l2 + k)
+            shift = k if lists == 6 else 5 * k
+            allowed = {c + shift for c in D.allowed_columns(l2) if c + shift < l2}
+            pairs, sites = D.dense_batch(rng, l1, l2, n, allowed)
+            sc = D.SCORINGS[k % 3]
+            for s1, s2 in pairs:
+                out.append(case("fit", s1, s2, *sc[:4], sc[4], True, sites, tag="dense %dx%d list %d" % (l1, l2, k), long=100))
+    return out
+
+
 def cli_cases():
     """Byte-exact behaviour of the stock reference CLI (stdout, stderr, rc)."""
     exe = os.path.join(ROOT, "oracle", "_ref", "alignTools")
@@ -276,6 +299,9 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     if sys.argv[1:3] == ["--only", "big"]:
         dump("known_answers_big.jsonl", known_answers_big())
+        return
+    if sys.argv[1:3] == ["--only", "dense"]:
+        dump("dense_sites.jsonl", dense_sites())
         return
     dump("known_answers.jsonl", known_answers())
     dump("random_small.jsonl", random_small(random.Random(20261003), 1500))

@@ -65,6 +65,9 @@ def draw_batch(rng):
         pairs.append((a, b))
     max_l2 = max(s[1] for s in shapes)
     sites = sorted(rng.sample(range(max_l2 + 3), min(max_l2, rng.choice([0, 1, 3, 8])))) if uj else []
+    if uj and os.environ.get("AT_FUZZ_DENSE_SITES"):          # the complement: everything listed but the drawn values (no extra draw: the seeds keep their streams)
+        drawn = set(sites)
+        sites = [c for c in range(-2, max_l2 + 3) if c not in drawn]
     tb = rng.random() < 0.8
     if os.environ.get("AT_FUZZ_TB") in ("0", "1"):          # a campaign of scores-only (0) or traceback (1) batches; the draw above keeps the seeds' streams
         tb = os.environ["AT_FUZZ_TB"] == "1"

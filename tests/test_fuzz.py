@@ -3,12 +3,18 @@
 seeds 11 and 12 miss: the 4-lane groups, 16 / 19 rows per lane on the 16-lane groups, the 32-lane groups, the packed overlap kernel with
 4 and 16 rows per lane, ragged frames and the ragged packed overlap."""
 import os
+import re
 
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 SEEN = {}
+
+# The seed of the dense-list campaign (test_fuzz_campaign_aimed, third aim), picked like 21 and 24 from what its draw reaches on the GPU, the
+# kernel class of every batch printed: fitj int32 (29 batches, 10 more scores only); packed x16 on 16x4 K9 / K13 / K16 / K19, 8x8 K13 / K16,
+# 4x16 K10 / K16, 2x32 K10 / K12; packed x4 on 1x64 K1 / K4; ragged frames 8x8 K5 with tracebacks (3) and scores only (1).
+DENSE_SEED = 51
 
 
 @pytest.mark.parametrize("seed", [11, 12, 21, 24])
@@ -22,26 +28,43 @@ def test_fuzz_campaign(seed):
     assert n >= 1500
 
 
-@pytest.mark.parametrize("aim", ["overlap and edit, scores only (the sweeps on the gap ramp)", "edit -u 1 (every form of the bit-parallel kernel)"])
+AIMED = {
+    "overlap and edit, scores only (the sweeps on the gap ramp)":
+        ({"AT_FUZZ_MODES": "overlap,edit", "AT_FUZZ_TB": "0"}, 31, ("overlap scores-only int32", "edit int32")),
+    "edit -u 1 (every form of the bit-parallel kernel)":
+        ({"AT_FUZZ_MODES": "edit", "AT_FUZZ_EDIT_UNIT": "1", "AT_MYERS_LANE_MIN_PAIRS": "1"}, 32, ("myers W2 64x1", "myers W16 64x1", "myers W32 64x1")),
+    "fit -s under dense site lists (every column listed but the drawn ones)":
+        ({"AT_FUZZ_MODES": "fitj", "AT_FUZZ_DENSE_SITES": "1"}, DENSE_SEED, ("fitj int32",)),
+}
+
+
+@pytest.mark.parametrize("aim", list(AIMED))
 def test_fuzz_campaign_aimed(aim):
     """Round 3's new sweeps get a campaign of their own: overlap without tracebacks and cell-by-cell edit distance (at_sweep.hip.h, RAMP),
-    and the bit-parallel kernel with one alignment per lane in all four widths (AT_MYERS_LANE_MIN_PAIRS = 1: small batches too)."""
+    and the bit-parallel kernel with one alignment per lane in all four widths (AT_MYERS_LANE_MIN_PAIRS = 1: small batches too).
+    The third: fit -s with the complement of the drawn site list (AT_FUZZ_DENSE_SITES: the jump may open at 0 .. 8 columns only), on
+    the int32 kernel and the packed group widths, ragged and uniform (tests/test_dense_sites.py aims at each family; this one draws)."""
     import fuzz_parity
-    env = ({"AT_FUZZ_MODES": "overlap,edit", "AT_FUZZ_TB": "0"} if aim.startswith("overlap")
-           else {"AT_FUZZ_MODES": "edit", "AT_FUZZ_EDIT_UNIT": "1", "AT_MYERS_LANE_MIN_PAIRS": "1"})
+    env, seed, families = AIMED[aim]
     os.environ.update(env)
     seen = {}
     try:
-        n = fuzz_parity.run(int(os.environ.get("AT_FUZZ_CASES", "1500")), 31 if aim.startswith("overlap") else 32, verbose=False, classes=seen)
+        n = fuzz_parity.run(int(os.environ.get("AT_FUZZ_CASES", "1500")), seed, verbose=False, classes=seen)
     finally:
         for k in env:
             del os.environ[k]
     assert n >= 1500
     keys = " | ".join(seen)
-    for family in (("overlap scores-only int32", "edit int32") if aim.startswith("overlap") else ("myers W2 64x1", "myers W16 64x1", "myers W32 64x1")):
+    for family in families:
         assert family in keys, (family, sorted(seen))
-    if not aim.startswith("overlap"):
+    if aim.startswith("edit"):
         assert sum(1 for k in seen if "myers" in k and "64x1" in k) >= 5, sorted(seen)   # (2, 3, 4, 5, 8, 16, 32 words per lane: most of them)
+    if aim.startswith("fit -s"):
+        assert all(k.startswith("fitj") for k in seen), sorted(seen)
+        packed = [k for k in seen if "packed16" in k]
+        widths = {re.search(r" (\d+x\d+) K", k).group(1) for k in packed}
+        assert len(widths) >= 3, sorted(seen)
+        assert any(" ragged" in k for k in packed) and any(" ragged" not in k for k in packed), sorted(seen)
 
 
 def test_fuzz_campaign_walk_kernel():

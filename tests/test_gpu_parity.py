@@ -63,11 +63,13 @@ def _run_group(al, key, cases):
         assert (gs["score"] == res["score"]).all() and (gs["nops"] == res["nops"]).all()
 
 
-@pytest.mark.parametrize("name", ["random_small.jsonl", "random_dna.jsonl", "known_answers.jsonl", "known_answers_big.jsonl"])
+@pytest.mark.parametrize("name", ["random_small.jsonl", "random_dna.jsonl", "known_answers.jsonl", "known_answers_big.jsonl", "dense_sites.jsonl"])
 def test_hip_matches_reference_goldens(al, name):
     groups = _group(load_golden(name))
     for key, cases in groups.items():
         _run_group(al, key, cases)
+        if name == "dense_sites.jsonl":     # one dense list = one batch of 32 or 8 pairs, on a packed kernel
+            assert len(cases) >= 8 and "packed16" in al.last_config, al.last_config
 
 
 def test_hip_matches_oracle_ops_and_end_cells(al):

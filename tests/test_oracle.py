@@ -29,7 +29,7 @@ def _check(case):
         assert _md5(r["r1"]) == case["r1_md5"] and _md5(r["r2"]) == case["r2_md5"], case["tag"]
 
 
-@pytest.mark.parametrize("name", ["known_answers.jsonl", "random_small.jsonl", "random_dna.jsonl"])
+@pytest.mark.parametrize("name", ["known_answers.jsonl", "random_small.jsonl", "random_dna.jsonl", "dense_sites.jsonl"])
 def test_oracle_matches_reference_goldens(name):
     cases = load_golden(name)
     assert len(cases) > 30
