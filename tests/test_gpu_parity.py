@@ -1168,6 +1168,54 @@ def test_bit_parallel_edit_distance(al):
         assert "int32" in al.last_config and int(res["score"][0]) == O.align(O.EDIT, a, b, 1, 1, -5, -1)["score"], al.last_config
 
 
+_LANE_GROUP_CLASSES = {4: ((2049, 4095, 4096), (1, 127, 128, 129)), 8: ((4097, 6000, 8191, 8192), (1, 255, 256, 257, 300)),
+                       16: ((8193, 12000, 16383, 16384), (1, 511, 512, 513))}
+_lane_group_runs = {}
+
+
+@pytest.mark.parametrize("words,which", [(w, k) for w in (4, 8, 16) for k in range(len(_LANE_GROUP_CLASSES[w][0]))],
+                         ids=["w%d-l%d" % (w, l) for w in (4, 8, 16) for l in _LANE_GROUP_CLASSES[w][0]])
+def test_bit_parallel_edit_distance_on_32_lane_groups(al, words, which):
+    """`edit -u 1` batches whose longest first sequence selects at_myers<4,32>, <8,32> and <16,32> (2 049 .. 4 096, 4 097 .. 8 192 and
+    8 193 .. 16 384 rows), named by at_last_config: the first and last length of each class, one inside and the last but one, in one
+    batch with first sequences that fill one lane's words exactly, one row less, one more, or a single row -- pairs on which most of
+    the 32 lanes hold no rows.  Per first sequence an unrelated second one of up to 3 000 bases, a related one and an identical
+    one, every score against the oracle.  One batch per class (run once); a test case checks the pairs of one long length, the
+    first of a class also those of the short ones."""
+    long_l1, short_l1 = _LANE_GROUP_CLASSES[words]
+    if words not in _lane_group_runs:
+        rng = random.Random(3200 + words)
+        dna = lambda n: "".join(rng.choice("ACGT") for _ in range(n))
+        def related(a):
+            t = list(a)
+            for _ in range(max(1, len(t) // 10)):
+                q = rng.randrange(len(t))
+                r = rng.random()
+                if r < 0.4:
+                    t[q] = rng.choice("ACGT")
+                elif r < 0.7 and len(t) > 1:
+                    del t[q]
+                else:
+                    t.insert(q, rng.choice("ACGT"))
+            return "".join(t)
+        pairs = []
+        for n in long_l1 + short_l1:
+            a = dna(n)
+            pairs += [(a, dna(rng.randint(1, 3000))), (a, related(a)), (a, a)]
+        al.set_scoring(1, 1, -5, -1)
+        res = al.align_batch("edit", pairs)
+        _lane_group_runs[words] = (pairs, [int(x) for x in res["score"]], al.last_config)
+    pairs, scores, cfg = _lane_group_runs[words]
+    assert "myers" in cfg and "words/lane=%d " % words in cfg and "2x32-lane" in cfg, cfg
+    mine = (long_l1[which],) + (short_l1 if which == 0 else ())
+    checked = 0
+    for k, (a, b) in enumerate(pairs):
+        if len(a) in mine:
+            assert scores[k] == O.align(O.EDIT, a, b, 1, 1, -5, -1)["score"], (words, k, len(a), len(b))
+            checked += 1
+    assert checked == 3 * len(mine)
+
+
 def test_device_entry_detects_uniform_batches_itself(al):
     """at_align_batch_device(uniform_shape = 0) on a batch that does have one shape: the device checks the lengths and the
     packed launch runs (the int32 launch queued behind it is a no-op); with one odd pair the roles swap.  Same results."""
@@ -1659,7 +1707,8 @@ def test_overlap_threshold_filter(al, shape):
     """All-vs-all overlap scores with a threshold (at_set_min_score; at_myers.hip.h, SEMI): pairs whose score is proven below T by the
     bit-parallel bound are not swept.  Against the unthresholded sweep of the same triangle: every pair the filter let through
     (state 2) carries the exact score and end cell; every pair it stopped (state 0) really scores below T, and the bound it reports
-    is one; unrelated reads are stopped, planted overlaps are not.  Read sets of mixed lengths, every word class of the filter."""
+    is one; unrelated reads are stopped, planted overlaps are not.  Read sets of mixed lengths; the five shapes reach the filter's
+    classes of 32, 32, 5, 2 and 16 words per lane (all seven classes, and the value of the bound: tests/test_overlap_filter.py)."""
     import torch
     import aligntools.c_amd as A
     lo, hi, n = shape
