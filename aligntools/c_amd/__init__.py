@@ -22,6 +22,9 @@ MODES = {"global": MODE_GLOBAL, "local": MODE_LOCAL, "fit": MODE_FIT, "overlap":
 STRAND_FWD, STRAND_REV, STRAND_BOTH = 1, 2, 3
 STRANDS = {"forward": STRAND_FWD, "reverse": STRAND_REV, "both": STRAND_BOTH}
 OP_MID, OP_LOW, OP_UPP, OP_JUMP = 0, 1, 2, 3
+CIGAR_M = 1                     # AT_CIGAR_M: '=' and 'X' merge into 'M'
+CIGAR_LETTERS = b"MIDNSHP=X"    # a CIGAR word is (run length << 4) | index into this
+ERR_ARG, ERR_DOMAIN = -1, -4
 ST_LOW, ST_MID, ST_UPP = 1, 2, 3
 
 # every symbol include/aligntools_hip.h declares
@@ -29,6 +32,7 @@ ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_s
                "at_align_batch_device", "at_align_allpairs_device", "at_render_batch_device", "at_compact_ops_device",
                "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream", "at_search",
                "at_search_strands", "at_revcomp", "at_revcomp_device",
+               "at_cigar", "at_cigar_batch_device", "at_align_batch_cigar",
                "at_comm_init", "at_comm_broadcast_scoring", "at_comm_allgather", "at_comm_destroy", "at_comm_abi_checked",
                "at_pack_words", "at_pack_batch", "at_render", "at_last_config"]
 
@@ -137,6 +141,13 @@ def load_library():
                                   C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.at_render.restype = C.c_int
     lib.at_render.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.at_cigar.restype = C.c_int
+    lib.at_cigar.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.at_cigar_batch_device.restype = C.c_int
+    lib.at_cigar_batch_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 4 + [
+        C.c_int64, C.c_void_p]
+    lib.at_align_batch_cigar.restype = C.c_int
+    lib.at_align_batch_cigar.argtypes = [C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 8 + [C.c_int64]
     _lib = lib
     return lib
 
@@ -203,6 +214,26 @@ def revcomp(s):
     if rc:
         raise AlignToolsError(rc, lib.at_last_error(None).decode())
     return out.raw[:len(s)]
+
+
+def cigar(ops, s1, end_i, s2, end_j, extended=True):
+    """Host helper (at_cigar): ops (END -> START) + end cell -> (words, stats): the run-length CIGAR as a numpy uint32 array of
+    (run length << 4) | BAM op code, in reading order, and the eight statistics (start_i, start_j, equal, unequal, I bases, D bases,
+    N bases, I runs + D runs) as a numpy int32 array.  extended: '=' / 'X'; else both are 'M'."""
+    lib = load_library()
+    ops, s1, s2 = bytes(ops), _b(s1), _b(s2)
+    words = np.zeros(max(1, len(ops)), dtype=np.uint32)
+    stats = np.zeros(8, dtype=np.int32)
+    nc = C.c_int32(0)
+    rc = lib.at_cigar(ops, len(ops), s1, int(end_i), s2, int(end_j), 0 if extended else CIGAR_M, _ptr(words), C.byref(nc), _ptr(stats))
+    if rc:
+        raise AlignToolsError(rc, "at_cigar: " + ("ops inconsistent with the sequences" if rc == ERR_DOMAIN else "bad argument"))
+    return words[:nc.value].copy(), stats
+
+
+def cigar_string(words):
+    """CIGAR words -> text, for example b"12=1X3I40="."""
+    return b"".join(b"%d%c" % (int(w) >> 4, CIGAR_LETTERS[int(w) & 15]) for w in words)
 
 
 def _flatten(pairs):
@@ -299,6 +330,38 @@ class Aligner:
         """Slots of ops -> one contiguous payload + exclusive offsets (at_compact_ops_device)."""
         self._check(self._lib.at_compact_ops_device(self._h, npairs, d_ops, d_ops_off, d_nops, d_packed, packed_cap,
                                                     d_packed_off, stream))
+
+    def cigar_batch_device(self, npairs, d_seq, bits, d_woff1, d_woff2, d_end_i, d_end_j, d_ops, d_ops_off, d_nops,
+                           d_ncigar, d_stats, d_cigar_off, d_cigar, cigar_cap, extended=True, stream=0):
+        """Raw device-pointer entry of the CIGAR kernel (at_cigar_batch_device)."""
+        self._check(self._lib.at_cigar_batch_device(self._h, npairs, d_seq, bits, d_woff1, d_woff2, d_end_i, d_end_j,
+                                                    d_ops, d_ops_off, d_nops, 0 if extended else CIGAR_M, d_ncigar, d_stats,
+                                                    d_cigar_off, d_cigar, cigar_cap, stream))
+
+    def align_batch_cigar(self, mode, pairs, extended=True):
+        """pairs: list of (s1, s2) bytes/str.  CIGARs and statistics made on the GPU (at_align_batch_cigar).  Returns a dict: score,
+        end_i, end_j, state, ncigar (numpy), stats (numpy int32 [n, 8]), cigar_off (numpy int64 [n + 1]) and cigar, a list of
+        numpy uint32 arrays of (run length << 4) | BAM op code in reading order."""
+        if isinstance(mode, str):
+            mode = MODES[mode]
+        pairs = [(_b(a), _b(b)) for a, b in pairs]
+        n = len(pairs)
+        blob, off1, len1, off2, len2 = _flatten(pairs)
+        score, end_i, end_j, state, ncigar = (np.zeros(n, dtype=np.int32) for _ in range(5))
+        stats = np.zeros((n, 8), dtype=np.int32)
+        cigar_off = np.zeros(n + 1, dtype=np.int64)
+        cap = 16 * n + 64                                      # a second call if the batch has more runs than that
+        for _ in range(2):
+            words = np.zeros(cap, dtype=np.uint32)
+            self._check(self._lib.at_align_batch_cigar(self._h, mode, n, _ptr(blob), _ptr(off1), _ptr(len1), _ptr(off2), _ptr(len2),
+                                                       0 if extended else CIGAR_M, _ptr(score), _ptr(end_i), _ptr(end_j),
+                                                       _ptr(state), _ptr(stats), _ptr(ncigar), _ptr(cigar_off), _ptr(words), cap))
+            if cigar_off[n] <= cap:
+                break
+            cap = int(cigar_off[n])
+        out = dict(score=score, end_i=end_i, end_j=end_j, state=state, ncigar=ncigar, stats=stats, cigar_off=cigar_off)
+        out["cigar"] = [words[cigar_off[k]:cigar_off[k] + ncigar[k]].copy() for k in range(n)]
+        return out
 
     def align_batch(self, mode, pairs, traceback=True, render=True):
         """pairs: list of (s1, s2) bytes/str.  Returns a dict of numpy arrays

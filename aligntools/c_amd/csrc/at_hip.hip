@@ -10,6 +10,7 @@
 #include "at_myers.hip.h"
 #include "at_search.hip.h"
 #include "at_revcomp.hip.h"
+#include "at_cigar.hip.h"
 #include "../../../include/aligntools_hip.h"
 
 #include <algorithm>
@@ -125,6 +126,13 @@ struct at_handle {
 	char err[512] = {0};
 	char cfg[640] = "none";
 	int last_render_lanes = 0;      /* lanes per pair of the latest at_render_batch_device (at_last_config of the host entry's strings) */
+	/* the host entry's CIGAR form: device block (counts, statistics, words), its page-locked mirror, and what a chunk leaves for the
+	 * parent to lay into the caller's buffer behind the join */
+	void *d_cg = nullptr; size_t cg_bytes = 0;
+	void *hp_cg = nullptr; size_t hp_cg_bytes = 0;
+	const uint32_t *cg_words = nullptr; int64_t cg_total = 0;
+	double last_cigar_per_pair = 4.0;      /* CIGAR words per pair of the latest batch: how many the next one fetches unasked */
+	int last_cigar_lanes = 0;       /* lanes per pair of the latest at_cigar_batch_device */
 };
 
 static thread_local char g_err[512] = "no error";   /* per thread: the host entry runs chunks on helper threads */
@@ -243,6 +251,8 @@ extern "C" void at_destroy(at_handle *h)
 	if (h->d_str) (void)hipFree(h->d_str);
 	if (h->d_scan) (void)hipFree(h->d_scan);
 	if (h->d_rflag) (void)hipFree(h->d_rflag);
+	if (h->d_cg) (void)hipFree(h->d_cg);
+	if (h->hp_cg) (void)hipHostFree(h->hp_cg);
 	if (h->h_pin) (void)hipHostFree(h->h_pin);
 	if (h->hp_desc) (void)hipHostFree(h->hp_desc);
 	if (h->hp_blob) (void)hipHostFree(h->hp_blob);
@@ -365,6 +375,51 @@ extern "C" int at_render(const uint8_t *ops, int32_t nops, const uint8_t *s1, in
 		}
 	}
 	r1[nops] = 0; r2[nops] = 0;
+	return AT_OK;
+}
+
+/* the CIGAR rule of include/aligntools_hip.h, one op at a time; the kernel (at_cigar.hip) computes the same from ballots */
+extern "C" int at_cigar(const uint8_t *ops, int32_t nops, const uint8_t *s1, int32_t end_i,
+                        const uint8_t *s2, int32_t end_j, int flags, uint32_t *cigar, int32_t *ncigar, int32_t stats[8])
+{
+	if (nops < 0 || end_i < 0 || end_j < 0 || !ncigar || !stats || (nops > 0 && (!ops || !s1 || !s2))) return AT_ERR_ARG;
+	const bool merge = (flags & AT_CIGAR_M) != 0;
+	/* two walks, as on the device: the first counts and checks, the second writes run r (from the END) to cigar[runs - 1 - r] */
+	int runs = 0;
+	for (int pass = 0; pass < 2; ++pass) {
+		int i = end_i, j = end_j, r = 0, cur = -1, len = 0;
+		int32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+		bool bad = false;
+		for (int k = 0; k < nops && !bad; ++k) {
+			int cls = -1;
+			switch (ops[k]) {
+			case AT_OP_MID: if (i <= 0 || j <= 0) { bad = true; break; } --i; --j; cls = s1[i] == s2[j] ? 7 : 8; ++st[cls == 7 ? AT_CG_EQUAL : AT_CG_UNEQUAL]; break;
+			case AT_OP_LOW: if (i <= 0) { bad = true; break; } --i; cls = 1; ++st[AT_CG_INS]; break;
+			case AT_OP_UPP: if (j <= 0) { bad = true; break; } --j; cls = 2; ++st[AT_CG_DEL]; break;
+			case AT_OP_JUMP: if (j <= 0) { bad = true; break; } --j; cls = 3; ++st[AT_CG_SKIP]; break;
+			default: bad = true; break;
+			}
+			if (bad) break;
+			const int rc = merge && cls >= 7 ? 0 : cls;
+			if (rc != cur) {
+				if (pass == 1 && cur >= 0) cigar[runs - r] = ((uint32_t)len << 4) | (uint32_t)cur;
+				if (cls == 1 || cls == 2) ++st[AT_CG_GAPS];
+				cur = rc; len = 0; ++r;
+			}
+			++len;
+		}
+		if (bad) {
+			*ncigar = -1;
+			for (int q = 0; q < 8; ++q) stats[q] = -1;
+			return AT_ERR_DOMAIN;
+		}
+		if (pass == 1 && cur >= 0) cigar[runs - r] = ((uint32_t)len << 4) | (uint32_t)cur;
+		st[AT_CG_START_I] = i; st[AT_CG_START_J] = j;
+		runs = r;
+		memcpy(stats, st, sizeof st);
+		*ncigar = runs;
+		if (!cigar) break;
+	}
 	return AT_OK;
 }
 
@@ -850,6 +905,43 @@ extern "C" int at_compact_ops_device(at_handle *h, int64_t npairs,
 		                   d_nops, d_packed, (const long long *)d_packed_off, (long long)packed_cap);
 	}
 	HIP_TRY(h, hipGetLastError());
+	return AT_OK;
+}
+
+extern "C" int at_cigar_batch_device(at_handle *h, int64_t npairs,
+                                     const uint32_t *d_seq, int bits,
+                                     const int64_t *d_woff1, const int64_t *d_woff2,
+                                     const int32_t *d_end_i, const int32_t *d_end_j,
+                                     const uint8_t *d_ops, const int64_t *d_ops_off, const int32_t *d_nops,
+                                     int flags, int32_t *d_ncigar, int32_t *d_stats, int64_t *d_cigar_off,
+                                     uint32_t *d_cigar, int64_t cigar_cap, void *stream_)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_cigar_batch_device: NULL handle");
+	if (npairs < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "negative size");
+	if (!d_cigar_off) return fail(h, AT_ERR_ARG, "NULL device pointer");
+	HIP_TRY(h, hipSetDevice(h->device));
+	drop_stale_error();
+	hipStream_t s = (hipStream_t)stream_;
+	if (npairs == 0) {
+		HIP_TRY(h, hipMemsetAsync(d_cigar_off, 0, 8, s));
+		return AT_OK;
+	}
+	if (bits != 2 && bits != 8) return fail(h, AT_ERR_ARG, "bits must be 2 or 8");
+	if (!d_seq || !d_woff1 || !d_woff2 || !d_end_i || !d_end_j || !d_ops || !d_ops_off || !d_nops || !d_ncigar || (!d_cigar && cigar_cap > 0))
+		return fail(h, AT_ERR_ARG, "NULL device pointer");
+	at::CigarArgs ca;
+	ca.npairs = npairs; ca.seq = d_seq; ca.woff1 = (const long long *)d_woff1; ca.woff2 = (const long long *)d_woff2;
+	ca.end_i = d_end_i; ca.end_j = d_end_j; ca.ops = d_ops; ca.ops_off = (const long long *)d_ops_off; ca.nops = d_nops;
+	ca.merge = (flags & AT_CIGAR_M) ? 1 : 0; ca.ncigar = d_ncigar; ca.stats = d_stats; ca.cigar_off = (const long long *)d_cigar_off;
+	ca.cigar = d_cigar; ca.cap = cigar_cap;
+	/* the group width of at_render_batch_device, by its rule and its knob (two widths are built: AT_RENDER_GROUP = 64 is one pair per
+	 * wavefront, every other value the 16-lane groups) */
+	const int w = env_ll("AT_RENDER_GROUP", h->last_span >= 1024 ? 64 : 16) == 64 ? 64 : 16;
+	h->last_cigar_lanes = w;
+	HIP_TRY(h, at_cigar_launch(&ca, bits, w, 0, h->ncu, s));
+	int rc = scan_nops_device(h, npairs, d_ncigar, d_cigar_off, s);
+	if (rc) return rc;
+	HIP_TRY(h, at_cigar_launch(&ca, bits, w, 1, h->ncu, s));
 	return AT_OK;
 }
 
@@ -1340,14 +1432,23 @@ static void htrace(const char *what, long long a)
 	fprintf(stderr, "[host %10.1f us] %s %lld\n", us, what, a);
 }
 
+/* the CIGAR form of the host entry (at_align_batch_cigar): what a chunk fills in.  The words stay in the chunk's own page-locked
+ * buffer (at_handle::cg_words, cg_total) until the parent lays the chunks' payloads back to back in pair order (cigar_gather) */
+struct CigarReq {
+	int flags;
+	int32_t *out_stats, *out_ncigar;
+	int64_t *out_off;              /* [n] the chunk's own exclusive offsets; the parent adds the words of the chunks before it */
+};
+
 /* host-buffer entry; with out_r1/out_r2 the strings are rendered on the GPU (slots of len1+len2+1 bytes at ops_off[k])
- * and the op codes stay on the device */
+ * and the op codes stay on the device; with cg neither comes down: CIGAR words and statistics do */
 static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq_blob,
                       const int64_t *off1, const int32_t *len1, const int64_t *off2, const int32_t *len2,
                       int want_traceback,
                       int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state,
                       uint8_t *out_ops, const int64_t *ops_off, int32_t *out_nops, char *out_r1, char *out_r2,
-                      int64_t pair_base = 0)   /* index of pair 0 in the caller's batch, for messages */
+                      int64_t pair_base = 0,   /* index of pair 0 in the caller's batch, for messages */
+                      const CigarReq *cg = nullptr)
 {
 	if (!h) return fail(nullptr, AT_ERR_ARG, "at_align_batch: NULL handle");
 	if (mode < AT_MODE_GLOBAL || mode > AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "unknown mode %d", mode);
@@ -1355,8 +1456,8 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	if (npairs == 0) return AT_OK;
 	if (!seq_blob || !off1 || !len1 || !off2 || !len2 || !out_score) return fail(h, AT_ERR_ARG, "NULL argument");
 	const bool tb = want_traceback && mode != AT_MODE_EDIT;
-	const bool strings = out_r1 != nullptr;
-	if (tb && ((!out_ops && !strings) || !ops_off || !out_nops)) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
+	const bool strings = out_r1 != nullptr, cigar = cg != nullptr;
+	if (tb && ((!out_ops && !strings && !cigar) || !ops_off || !out_nops)) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
 
 	int max1 = 0, max2 = 0;
 	bool uniform = true;
@@ -1706,7 +1807,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	 * ---- caller's buffers between and behind the slots are never touched, whatever order the slots are in. ---- */
 	const size_t res_bytes = 5 * b_len1;
 	const size_t b_str = al((size_t)slots_total + (size_t)npairs + 64);
-	const size_t pk_cap = tb ? (strings ? 2 : 1) * b_str : 0;
+	const size_t pk_cap = tb && !cigar ? (strings ? 2 : 1) * b_str : 0;
 	rc = grow_pinned(h, &h->hp_out, &h->hp_out_bytes, res_bytes + 64 + (tb ? b_pfx : 0) + pk_cap);
 	if (rc) return rc;
 	char *ho = (char *)h->hp_out;
@@ -1717,7 +1818,29 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	*p_rflag = 0;
 	uint8_t *d_pk1 = nullptr, *d_pk2 = nullptr;
 	size_t spec = 0;                                   /* payload bytes fetched before the total is known */
-	if (tb) {
+	/* the CIGAR form: counts | statistics | words in one device block; counts and statistics come down in one copy, the offsets in a
+	 * second, and as many words as the previous call's payload suggests in a third */
+	const size_t c_head = al(n * 4) + al(n * 32), c_pfx = al((n + 1) * 8);
+	size_t spec_w = 0;
+	if (cigar) {
+		rc = grow(h, &h->d_cg, &h->cg_bytes, c_head + (size_t)slots_total * 4 + 64);
+		if (rc) return rc;
+		char *dc = (char *)h->d_cg;
+		rc = at_cigar_batch_device(h, npairs, d_words, bits, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_opsoff, d_nops, cg->flags,
+		                           (int32_t *)dc, (int32_t *)(dc + al(n * 4)), d_poff, (uint32_t *)(dc + c_head), slots_total, s);
+		if (rc) return rc;
+		snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " [cigar: %d lanes per pair]", h->last_cigar_lanes);
+		/* (the guess is the ops form's, not a measurement of this one: the last batch's payload per pair and a quarter more, and the
+		 * same 64 KiB floor; a handle's first batch assumes four runs per pair) */
+		spec_w = std::min<size_t>((size_t)slots_total, (size_t)(h->last_cigar_per_pair * 1.25 * (double)npairs) + 16384);
+		rc = grow_pinned(h, &h->hp_cg, &h->hp_cg_bytes, c_head + c_pfx + spec_w * 4);
+		if (rc) return rc;
+		char *hc = (char *)h->hp_cg;
+		HIP_TRY(h, hipMemcpyAsync(hc, dc, c_head, hipMemcpyDeviceToHost, s));
+		HIP_TRY(h, hipMemcpyAsync(hc + c_head, d_poff, (size_t)(npairs + 1) * 8, hipMemcpyDeviceToHost, s));
+		if (spec_w) HIP_TRY(h, hipMemcpyAsync(hc + c_head + c_pfx, dc + c_head, spec_w * 4, hipMemcpyDeviceToHost, s));
+	}
+	if (tb && !cigar) {
 		rc = grow(h, &h->d_str, &h->str_bytes, (strings ? 2 : 1) * b_str + (strings ? b_pfx : 0));
 		if (rc) return rc;
 		d_pk1 = (uint8_t *)h->d_str; d_pk2 = d_pk1 + b_str;
@@ -1754,7 +1877,38 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	if (out_end_i) memcpy(out_end_i, ho + b_len1, (size_t)npairs * 4);
 	if (out_end_j) memcpy(out_end_j, ho + 2 * b_len1, (size_t)npairs * 4);
 	if (out_state) memcpy(out_state, ho + 3 * b_len1, (size_t)npairs * 4);
-	if (tb) {
+	if (cigar) {
+		memcpy(out_nops, r_nops, (size_t)npairs * 4);
+		const char *hc = (const char *)h->hp_cg;
+		const int32_t *r_nc = (const int32_t *)hc;
+		const int64_t *r_off = (const int64_t *)(hc + c_head);
+		const int64_t total = r_off[(size_t)npairs];
+		if (total < 0 || total > slots_total) return fail(h, AT_ERR_DOMAIN, "CIGAR lengths inconsistent with the slots");
+		for (int64_t k = 0; k < npairs; ++k)
+			if (r_nc[k] < 0) return fail(h, AT_ERR_DOMAIN, "pair %lld: traceback inconsistent with its sequences", (long long)(pair_base + k));
+		memcpy(cg->out_ncigar, r_nc, (size_t)npairs * 4);
+		memcpy(cg->out_stats, hc + al(n * 4), (size_t)npairs * 32);
+		memcpy(cg->out_off, r_off, (size_t)npairs * 8);
+		h->last_cigar_per_pair = (double)total / (double)npairs;
+		if ((size_t)total > spec_w) {       /* more runs than the last batch's: the rest of the payload, as the other two forms do */
+			const size_t need = c_head + c_pfx + (size_t)total * 4;
+			if (need > h->hp_cg_bytes) {    /* ... into a larger buffer; the words that are down already move over */
+				void *nb = nullptr;
+				size_t nbytes = 0;
+				rc = grow_pinned(h, &nb, &nbytes, need);
+				if (rc) return rc;
+				memcpy((char *)nb + c_head + c_pfx, (const char *)h->hp_cg + c_head + c_pfx, spec_w * 4);
+				(void)hipHostFree(h->hp_cg);
+				h->hp_cg = nb; h->hp_cg_bytes = nbytes;
+			}
+			HIP_TRY(h, hipMemcpyAsync((char *)h->hp_cg + c_head + c_pfx + spec_w * 4, (const char *)h->d_cg + c_head + spec_w * 4,
+			                          ((size_t)total - spec_w) * 4, hipMemcpyDeviceToHost, s));
+			HIP_TRY(h, hipStreamSynchronize(s));
+		}
+		h->cg_words = (const uint32_t *)((const char *)h->hp_cg + c_head + c_pfx);
+		h->cg_total = total;
+	}
+	if (tb && !cigar) {
 		memcpy(out_nops, r_nops, (size_t)npairs * 4);
 		const int64_t total = h_poff[(size_t)npairs];
 		if (total < 0 || total > slots_total) return fail(h, AT_ERR_DOMAIN, "traceback lengths inconsistent with the slots");
@@ -1788,8 +1942,29 @@ static int align_host_mt(at_handle *h, int mode, int64_t npairs, const uint8_t *
                          const int64_t *off1, const int32_t *len1, const int64_t *off2, const int32_t *len2,
                          int want_traceback,
                          int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state,
-                         uint8_t *out_ops, const int64_t *ops_off, int32_t *out_nops, char *out_r1, char *out_r2)
+                         uint8_t *out_ops, const int64_t *ops_off, int32_t *out_nops, char *out_r1, char *out_r2,
+                         const CigarReq *cg = nullptr, uint32_t *out_cigar = nullptr, int64_t cigar_cap = 0)
 {
+	/* the CIGAR form, behind the join: chunk c's words lie in its handle's page-locked buffer and its offsets count from its own
+	 * first pair.  The payloads go back to back in pair order into the caller's buffer -- of a chunk that crosses the capacity, the
+	 * pairs that end within it -- and the offsets become the batch's (out_off[npairs] = total words) */
+	auto cigar_gather = [&](int nch, int64_t per_chunk) {
+		int64_t base = 0;
+		for (int c = 0; c < nch; ++c) {
+			const int64_t lo = std::min<int64_t>(npairs, c * per_chunk), nn = std::min<int64_t>(npairs, lo + per_chunk) - lo;
+			if (nn <= 0) continue;
+			const at_handle *hh = c == 0 ? h : h->kids[(size_t)c - 1];
+			int64_t fit = 0;               /* words of the chunk's leading pairs that end within the capacity */
+			for (int64_t k = 0; k < nn; ++k) {
+				const int64_t end = base + cg->out_off[lo + k] + cg->out_ncigar[lo + k];
+				if (end <= cigar_cap) fit = end - base;
+				cg->out_off[lo + k] += base;
+			}
+			if (fit > 0) memcpy(out_cigar + base, hh->cg_words, (size_t)fit * 4);
+			base += hh->cg_total;
+		}
+		cg->out_off[npairs] = base;
+	};
 	/* uniform batches: six chunks (100k pairs of C2: 3.37 ms in one piece, 2.49 in 3 chunks, 2.28 in 6); ragged ones, whose chunks are
 	 * sorted into frames one by one: three (fit -s 100..150 x 400..500: 785 GCUPS in 3 chunks, 693 in 6 -- smaller frames) */
 	htrace("batch: enter, pairs", npairs);
@@ -1800,9 +1975,15 @@ static int align_host_mt(at_handle *h, int mode, int64_t npairs, const uint8_t *
 	int nchunks = (int)std::max<long long>(1, std::min<long long>(want, 12));
 	if (!h || npairs < 2 * min_pairs || !seq_blob || !off1 || !len1 || !off2 || !len2 || !out_score) nchunks = 1;
 	else nchunks = (int)std::min<long long>(nchunks, npairs / min_pairs);
-	if (nchunks <= 1)
+	if (nchunks <= 1 && !cg)
 		return align_host(h, mode, npairs, seq_blob, off1, len1, off2, len2, want_traceback, out_score, out_end_i, out_end_j,
 		                  out_state, out_ops, ops_off, out_nops, out_r1, out_r2);
+	if (nchunks <= 1) {
+		const int rc = align_host(h, mode, npairs, seq_blob, off1, len1, off2, len2, want_traceback, out_score, out_end_i, out_end_j,
+		                          out_state, out_ops, ops_off, out_nops, out_r1, out_r2, 0, cg);
+		if (rc == AT_OK && npairs > 0) cigar_gather(1, npairs);
+		return rc;
+	}
 	while ((int)h->kids.size() < nchunks - 1) {
 		at_handle *k = nullptr;
 		const int dev = h->device;
@@ -1827,11 +2008,13 @@ static int align_host_mt(at_handle *h, int mode, int64_t npairs, const uint8_t *
 		at_handle *hh = c == 0 ? h : h->kids[(size_t)c - 1];
 		if (n <= 0) return;
 		/* (a chunk runs on a pool thread: an exception that left it would end the process in std::terminate) */
+		CigarReq mine;
+		if (cg) { mine.flags = cg->flags; mine.out_stats = cg->out_stats + 8 * lo; mine.out_ncigar = cg->out_ncigar + lo; mine.out_off = cg->out_off + lo; }
 		rcs[(size_t)c] = guarded(hh, "at_align_batch", [&] {
 			return align_host(hh, mode, n, seq_blob, off1 + lo, len1 + lo, off2 + lo, len2 + lo, want_traceback,
 			                  out_score + lo, out_end_i ? out_end_i + lo : nullptr, out_end_j ? out_end_j + lo : nullptr,
 			                  out_state ? out_state + lo : nullptr, out_ops, ops_off ? ops_off + lo : nullptr,
-			                  out_nops ? out_nops + lo : nullptr, out_r1, out_r2, lo);
+			                  out_nops ? out_nops + lo : nullptr, out_r1, out_r2, lo, cg ? &mine : nullptr);
 		});
 	};
 	if (!h->pool) h->pool = new HostPool();
@@ -1843,6 +2026,7 @@ static int align_host_mt(at_handle *h, int mode, int64_t npairs, const uint8_t *
 			return rcs[(size_t)c];
 		}
 	}
+	if (cg) cigar_gather(nchunks, per);
 	snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " x%d chunks", nchunks);
 	return AT_OK;
 }
@@ -2358,5 +2542,31 @@ extern "C" int at_align_batch_strings(at_handle *h, int mode, int64_t npairs, co
 	return guarded(h, "at_align_batch_strings", [&] {
 		return align_host_mt(h, mode, npairs, seq_blob, off1, len1, off2, len2, 1, out_score, out_end_i, out_end_j, out_state,
 		                     nullptr, str_off, out_len, out_r1, out_r2);
+	});
+}
+
+extern "C" int at_align_batch_cigar(at_handle *h, int mode, int64_t npairs, const uint8_t *seq_blob,
+                                    const int64_t *off1, const int32_t *len1, const int64_t *off2, const int32_t *len2,
+                                    int flags,
+                                    int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state,
+                                    int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
+                                    uint32_t *out_cigar, int64_t cigar_cap)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_align_batch_cigar: NULL handle");
+	if (mode == AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "edit has no alignment, hence no CIGAR (alignment.h:291)");
+	if (npairs < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "negative size");
+	if (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)) return fail(h, AT_ERR_ARG, "NULL CIGAR buffers");
+	if (npairs == 0) { out_cigar_off[0] = 0; return AT_OK; }
+	if (!seq_blob || !off1 || !len1 || !off2 || !len2 || !out_score) return fail(h, AT_ERR_ARG, "NULL argument");
+	return guarded(h, "at_align_batch_cigar", [&] {
+		/* the op codes stay on the device, in slots of len1 + len2 bytes laid back to back */
+		std::vector<int64_t> slot((size_t)npairs);
+		std::vector<int32_t> nops((size_t)npairs);
+		int64_t at = 0;
+		for (int64_t k = 0; k < npairs; ++k) { slot[(size_t)k] = at; at += (int64_t)std::max(len1[k], 0) + std::max(len2[k], 0); }
+		CigarReq cg;
+		cg.flags = flags; cg.out_stats = out_stats; cg.out_ncigar = out_ncigar; cg.out_off = out_cigar_off;
+		return align_host_mt(h, mode, npairs, seq_blob, off1, len1, off2, len2, 1, out_score, out_end_i, out_end_j, out_state,
+		                     nullptr, slot.data(), nops.data(), nullptr, nullptr, &cg, out_cigar, cigar_cap);
 	});
 }

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "at_seqbase.hip.h"   /* render_base */
+
 namespace at {
 
 struct RenderArgs {
@@ -28,19 +30,6 @@ struct RenderArgs {
 	int nul;                       /* write a terminating 0 behind each string */
 	int *bad;                      /* set to 1 if an op list walks off its sequences */
 };
-
-template <int BITS>
-__device__ __forceinline__ uint32_t render_base(const uint32_t *seq, long long woff, int idx)
-{
-	if constexpr (BITS == 2) {
-		const uint32_t w = seq[woff + (idx >> 4)];
-		const uint32_t code = (w >> (2 * (idx & 15))) & 3u;
-		return (0x54474341u >> (8 * code)) & 0xffu;            /* 0..3 -> 'A','C','G','T' */
-	} else {
-		const uint32_t w = seq[woff + (idx >> 2)];
-		return (w >> (8 * (idx & 3))) & 0xffu;
-	}
-}
 
 /* W lanes per pair, 64 / W pairs per wavefront side by side.  An alignment of unrelated 150-base reads has a dozen ops, one of
  * 36-base reads fewer: with one pair per wavefront the kernel is a chain of four dependent loads per pair with most lanes idle

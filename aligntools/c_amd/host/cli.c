@@ -9,6 +9,7 @@
  *     records (2k, 2k+1) of the file form pair k; all pairs go to the GPU in one batch.
  *   alignTools batch <command> [options] --queries <queries.fa> [--best K] [--both-strands] <targets.fa>
  *     every query against every target; the best K hits of each query are printed.
+ *   ... --paf (both forms, not edit): one PAF line per pair / hit (at_align_batch_cigar) instead of the name line and two strings.
  */
 #define _POSIX_C_SOURCE 200809L
 #include "at_host.h"
@@ -123,7 +124,7 @@ static int main_single(int cmd, int argc, char *argv[])
 }
 
 /* ---- batch extension: N pairs per file ----
- *   alignTools batch <command> [options] [--score-only] [--all-vs-all] [--gpus N] <pairs.fa>
+ *   alignTools batch <command> [options] [--score-only] [--all-vs-all] [--gpus N] [--paf] <pairs.fa>
  *     default        records (2k, 2k+1) form pair k
  *     --all-vs-all   the records are reads; every ordered pair a < b is aligned as s1 = read a, s2 = read b (not for fit)
  *     --score-only   no tracebacks: one line per pair (name1, name2, score)
@@ -137,6 +138,10 @@ static int main_single(int cmd, int argc, char *argv[])
  *                    --both-strands also searches every query's reverse complement (at_search_strands; made on the GPU): a hit's
  *                    header line gets a fourth column, + or -, and the strings of a - hit are those of the reverse-complemented
  *                    query; ties on score and target: + first.
+ *     --paf          one PAF line per pair / hit instead of the name line and the two strings: the twelve columns (mapq 255), AS:i,
+ *                    NM:i and cg:Z with the =/X CIGAR, from at_align_batch_cigar -- statistics rows and CIGAR words come down, no
+ *                    strings.  A - hit of --both-strands has its query coordinates on the query as given.  Not for edit,
+ *                    --score-only, --all-vs-all, --gpus N > 1.
  *     --gpus N       one process per GPU: this process starts N workers (itself, with AT_RANK / AT_WORLD / AT_DEVICE /
  *                    AT_COMM_DIR in their environment), rank 0's options are broadcast over RCCL, every rank aligns a
  *                    contiguous share of the pairs on its own GPU, results are gathered over RCCL and rank 0 prints them
@@ -145,7 +150,7 @@ static int main_single(int cmd, int argc, char *argv[])
  * thread -- which also pays the HIP start-up, in the shadow of the first chunks' parsing -- sends each chunk to the GPU
  * and writes its results with one fwrite.  Memory is bounded by the chunks in flight, whatever the size of the file;
  * --all-vs-all keeps the read set and streams slices of the triangle instead (at_align_allpairs_stream). */
-typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both; } batch_flags;
+typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf; } batch_flags;
 
 /* linear index p of the strict upper triangle of n x n (row-major) -> (a, b), a < b: closed form + integer correction */
 static void tri_seek(int64_t p, int64_t n, int64_t *a, int64_t *b)
@@ -202,6 +207,29 @@ static void tb_pair(tbuf *t, const char *na, const char *nb, int32_t score, int 
 {
 	tb_pair_strand(t, na, nb, score, is_edit, 0, r1, r2, rl);
 }
+/* --paf: one PAF line per pair / hit.  qname qlen qstart qend strand tname tlen tstart tend <equal columns> <equal + unequal + I + D
+ * bases> 255, then AS:i:<score>, NM:i:<unequal + I + D> and, when there are runs, cg:Z:<the =/X CIGAR>.  A - hit was aligned as the
+ * reverse complement of its query: its query coordinates are given on the query as it stands in the file. */
+static void tb_paf(tbuf *t, const char *qn, int32_t ql, char strand, const char *tn, int32_t tl, int32_t score,
+                   int32_t end_i, int32_t end_j, const int32_t *st, const uint32_t *cg, int32_t ncg)
+{
+	const size_t la = strlen(qn), lb = strlen(tn);
+	const int32_t si = st[AT_CG_START_I], sj = st[AT_CG_START_J];
+	const int32_t qs = strand == '-' ? ql - end_i : si, qe = strand == '-' ? ql - si : end_i;
+	const int32_t gaps = st[AT_CG_INS] + st[AT_CG_DEL];
+	int32_t r;
+	tb_need(t, la + lb + 256 + (size_t)(ncg > 0 ? ncg : 0) * 12);
+	memcpy(t->s + t->l, qn, la); t->l += la;
+	t->l += (size_t)sprintf(t->s + t->l, "\t%d\t%d\t%d\t%c\t", (int)ql, (int)qs, (int)qe, strand);
+	memcpy(t->s + t->l, tn, lb); t->l += lb;
+	t->l += (size_t)sprintf(t->s + t->l, "\t%d\t%d\t%d\t%d\t%d\t255\tAS:i:%d\tNM:i:%d", (int)tl, (int)sj, (int)end_j, (int)st[AT_CG_EQUAL],
+	                        (int)(st[AT_CG_EQUAL] + st[AT_CG_UNEQUAL] + gaps), (int)score, (int)(st[AT_CG_UNEQUAL] + gaps));
+	if (ncg > 0) {
+		memcpy(t->s + t->l, "\tcg:Z:", 6); t->l += 6;
+		for (r = 0; r < ncg; ++r) t->l += (size_t)sprintf(t->s + t->l, "%u%c", (unsigned)(cg[r] >> 4), "MIDNSHP=X"[cg[r] & 15u]);
+	}
+	t->s[t->l++] = '\n';
+}
 static void tb_flush(tbuf *t)
 {
 	if (t->l && fwrite(t->s, 1, t->l, stdout) != t->l) die("write error on stdout");
@@ -215,6 +243,12 @@ typedef struct {
 	int32_t *l1, *l2, *score, *ei, *ej, *st, *nops;
 	char *r1, *r2;
 	size_t rcap;
+	/* --paf: statistics rows, run counts, offsets and CIGAR words instead of the strings */
+	int paf;
+	int32_t *stats, *ncg;
+	int64_t *cgoff;
+	uint32_t *cg;
+	int64_t cgcap;
 } slice_t;
 
 static void slice_reserve(slice_t *w, int64_t n)
@@ -227,11 +261,15 @@ static void slice_reserve(slice_t *w, int64_t n)
 	w->score = (int32_t *)at_xrealloc(w->score, (size_t)w->cap * 4); w->ei = (int32_t *)at_xrealloc(w->ei, (size_t)w->cap * 4);
 	w->ej = (int32_t *)at_xrealloc(w->ej, (size_t)w->cap * 4); w->st = (int32_t *)at_xrealloc(w->st, (size_t)w->cap * 4);
 	w->nops = (int32_t *)at_xrealloc(w->nops, (size_t)w->cap * 4);
+	if (w->paf) {
+		w->stats = (int32_t *)at_xrealloc(w->stats, (size_t)w->cap * 32); w->ncg = (int32_t *)at_xrealloc(w->ncg, (size_t)w->cap * 4);
+		w->cgoff = (int64_t *)at_xrealloc(w->cgoff, (size_t)(w->cap + 1) * 8);
+	}
 }
 static void slice_free(slice_t *w)
 {
 	free(w->off1); free(w->off2); free(w->slot); free(w->l1); free(w->l2); free(w->score); free(w->ei); free(w->ej); free(w->st);
-	free(w->nops); free(w->r1); free(w->r2);
+	free(w->nops); free(w->r1); free(w->r2); free(w->stats); free(w->ncg); free(w->cgoff); free(w->cg);
 	memset(w, 0, sizeof *w);
 }
 /* off1 / l1 / off2 / l2 of pairs 0 .. n-1 are filled in: align them (strings rendered on the GPU when tb) */
@@ -246,7 +284,19 @@ static void slice_run(slice_t *w, at_handle *h, int cmd, int tb, const uint8_t *
 		w->slot[k] = sl; sl += (int64_t)w->l1[k] + w->l2[k] + 1;
 	}
 	if (n <= 0) return;
-	if (tb) {
+	if (tb && w->paf) {
+		/* the words of a batch of reads are a few per pair: a buffer that does not hold them is grown once, to the total the call reports */
+		int pass;
+		rc = AT_OK;
+		for (pass = 0; pass < 2; ++pass) {
+			const int64_t want = pass == 0 ? 16 * n + 64 : w->cgoff[n];
+			if (pass == 1 && want <= w->cgcap) break;
+			if (want > w->cgcap) { w->cgcap = want + want / 4; free(w->cg); w->cg = (uint32_t *)at_xmalloc((size_t)w->cgcap * 4); }
+			rc = at_align_batch_cigar(h, mode, n, blob, w->off1, w->l1, w->off2, w->l2, 0, w->score, w->ei, w->ej, w->st, w->stats, w->ncg,
+			                          w->cgoff, w->cg, w->cgcap);
+			if (rc != AT_OK) break;
+		}
+	} else if (tb) {
 		if ((size_t)sl + 64 > w->rcap) {
 			w->rcap = (size_t)sl + (size_t)sl / 4 + 64;
 			free(w->r1); free(w->r2);
@@ -299,7 +349,7 @@ typedef struct {
 	at_chunk chunk[RING];
 	int filled[RING];            /* 1: parsed, waiting for the GPU thread */
 	int head, tail, closed;      /* the reader fills `tail`, the GPU thread takes `head` */
-	int cmd, tb;
+	int cmd, tb, paf;
 	opt_t *opt;
 } pipe_t;
 
@@ -313,6 +363,7 @@ static void *pipe_consumer(void *arg)
 	int rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, opt->s == AT_TRUE, opt->sites.pos, (int)opt->sites.size);
 	if (rc != AT_OK) die("%s", at_last_error(h));
 	memset(&w, 0, sizeof w);
+	w.paf = pp->paf;
 	trace("gpu handle ready", 0);
 	for (;;) {
 		at_chunk *c;
@@ -331,8 +382,12 @@ static void *pipe_consumer(void *arg)
 		slice_run(&w, h, pp->cmd, pp->tb, c->blob, n);
 		trace("chunk aligned, pairs", n);
 		for (k = 0; k < n; ++k)
-			tb_pair(&out, c->names + c->name_off[2 * k], c->names + c->name_off[2 * k + 1], w.score[k], pp->cmd == C_EDIT,
-			        pp->tb ? w.r1 + w.slot[k] : NULL, pp->tb ? w.r2 + w.slot[k] : NULL, pp->tb ? (size_t)w.nops[k] : 0);
+			if (pp->paf)
+				tb_paf(&out, c->names + c->name_off[2 * k], w.l1[k], '+', c->names + c->name_off[2 * k + 1], w.l2[k], w.score[k], w.ei[k], w.ej[k],
+				       w.stats + 8 * k, w.cg + w.cgoff[k], w.ncg[k]);
+			else
+				tb_pair(&out, c->names + c->name_off[2 * k], c->names + c->name_off[2 * k + 1], w.score[k], pp->cmd == C_EDIT,
+				        pp->tb ? w.r1 + w.slot[k] : NULL, pp->tb ? w.r2 + w.slot[k] : NULL, pp->tb ? (size_t)w.nops[k] : 0);
 		tb_flush(&out);
 		trace("chunk written", n);
 		pthread_mutex_lock(&pp->mu);
@@ -346,7 +401,7 @@ static void *pipe_consumer(void *arg)
 	return NULL;
 }
 
-static int batch_stream_pairs(int cmd, opt_t *opt, int tb, at_reader *rd)
+static int batch_stream_pairs(int cmd, opt_t *opt, int tb, int paf, at_reader *rd)
 {
 	pipe_t *pp = (pipe_t *)at_xmalloc(sizeof *pp);
 	pthread_t th;
@@ -357,7 +412,7 @@ static int batch_stream_pairs(int cmd, opt_t *opt, int tb, at_reader *rd)
 	memset(pp, 0, sizeof *pp);
 	pthread_mutex_init(&pp->mu, NULL);
 	pthread_cond_init(&pp->cv, NULL);
-	pp->cmd = cmd; pp->tb = tb; pp->opt = opt;
+	pp->cmd = cmd; pp->tb = tb; pp->paf = paf; pp->opt = opt;
 	for (;;) {
 		at_chunk *c;
 		size_t got;
@@ -440,8 +495,9 @@ static int batch_worker(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	const int64_t chunk_pairs = env_pos("AT_CLI_CHUNK", 32768) * 8;
 	if (!rd) die("Can't open %s\n", fname);
 	if (bf->all_vs_all && cmd == C_FIT) die("--all-vs-all: fit needs ordered pairs (first sequence shorter than the second)");
+	if (bf->paf && comm) die("--paf runs in one process");
 	if (!bf->all_vs_all && !comm) {
-		rc = batch_stream_pairs(cmd, opt, tb, rd);
+		rc = batch_stream_pairs(cmd, opt, tb, bf->paf, rd);
 		at_reader_close(rd);
 		return rc;
 	}
@@ -636,6 +692,7 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	for (q = 0; q < nq; ++q) nhit += nh[q];
 	if (tb && nhit > 0) {
 		const uint8_t *blob = c.blob;
+		w.paf = bf->paf;
 		slice_reserve(&w, nhit);
 		if (bf->both) {
 			/* the strings of a - hit are those of the reverse-complemented query: a second blob, the records and behind them the
@@ -671,8 +728,12 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	x = 0;
 	for (q = 0; q < nq; ++q) {
 		for (j = 0; j < nh[q]; ++j, ++x)
-			tb_pair_strand(&out, c.names + c.name_off[q], c.names + c.name_off[nq + tgt[q * kb + j]], sc[q * kb + j], cmd == C_EDIT,
-			        sd ? (sd[q * kb + j] == 1 ? '-' : '+') : 0, tb ? w.r1 + w.slot[x] : NULL, tb ? w.r2 + w.slot[x] : NULL, tb ? (size_t)w.nops[x] : 0);
+			if (bf->paf)
+				tb_paf(&out, c.names + c.name_off[q], qlen[q], sd && sd[q * kb + j] == 1 ? '-' : '+', c.names + c.name_off[nq + tgt[q * kb + j]],
+				       tlen[tgt[q * kb + j]], w.score[x], w.ei[x], w.ej[x], w.stats + 8 * x, w.cg + w.cgoff[x], w.ncg[x]);
+			else
+				tb_pair_strand(&out, c.names + c.name_off[q], c.names + c.name_off[nq + tgt[q * kb + j]], sc[q * kb + j], cmd == C_EDIT,
+				        sd ? (sd[q * kb + j] == 1 ? '-' : '+') : 0, tb ? w.r1 + w.slot[x] : NULL, tb ? w.r2 + w.slot[x] : NULL, tb ? (size_t)w.nops[x] : 0);
 		if (out.l > ((size_t)8 << 20)) tb_flush(&out);
 	}
 	tb_flush(&out);
@@ -742,10 +803,10 @@ static int main_batch(int argc, char *argv[], char *argv0)
 {
 	int cmd = -1, k, n = 0;
 	opt_t *opt = init_opt();
-	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0};
+	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0};
 	char **av = (char **)at_xmalloc((size_t)(argc + 1) * sizeof(char *));
-	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] <pairs.fa>\n"
-	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] <targets.fa>\n";
+	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] [--paf] <pairs.fa>\n"
+	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] <targets.fa>\n";
 	/* the long flags of the extension are taken out before getopt sees the reference's short options */
 	for (k = 0; k < argc; ++k) {
 		if (strcmp(argv[k], "--score-only") == 0) bf.score_only = 1;
@@ -755,6 +816,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (strcmp(argv[k], "--queries") == 0 && k + 1 < argc) bf.queries = argv[++k];
 		else if (strcmp(argv[k], "--best") == 0 && k + 1 < argc) { bf.best = atoi(argv[++k]); bf.best_set = 1; }
 		else if (strcmp(argv[k], "--both-strands") == 0) bf.both = 1;
+		else if (strcmp(argv[k], "--paf") == 0) bf.paf = 1;
 		else av[n++] = argv[k];
 	}
 	av[n] = NULL;
@@ -770,6 +832,10 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (bf.best_set && !bf.queries) why = "--best goes with --queries";
 		else if (bf.both && !bf.queries) why = "--both-strands goes with --queries";
 		else if (bf.queries && (bf.best < 1 || bf.best > 64)) why = "--best K needs 1 <= K <= 64";
+		else if (bf.paf && cmd == C_EDIT) why = "--paf does not go with edit (edit has no alignment)";
+		else if (bf.paf && bf.score_only) why = "--paf does not go with --score-only (a PAF line needs the traceback)";
+		else if (bf.paf && bf.all_vs_all) why = "--paf does not go with --all-vs-all";
+		else if (bf.paf && bf.gpus > 1) why = "--paf runs on one GPU: it does not go with --gpus N > 1";
 		if (why) { fprintf(stderr, "%s\n%s", why, usage_line); free(opt); free(av); return 1; }
 	}
 	if (bf.min_on && !bf.queries && !(cmd == C_OVERLAP && bf.all_vs_all && bf.score_only)) {

@@ -283,6 +283,57 @@ int at_align_batch_strings(at_handle *h, int mode, int64_t npairs,
                            char *out_r1, char *out_r2, const int64_t *str_off, int32_t *out_len);
 
 /*
+ * Run-length CIGARs and alignment statistics: what a mapper's users consume, made from the op codes, the end cell
+ * and the two sequences.  A column's class is a BAM op code of "MIDNSHP=X": AT_OP_MID with equal bytes '=' (7), with unequal bytes
+ * 'X' (8), AT_OP_LOW 'I' (1), AT_OP_UPP 'D' (2), AT_OP_JUMP 'N' (3, the spliced gap of fit -s); with AT_CIGAR_M in `flags`, '=' and
+ * 'X' are both 'M' (0) and merge into one run.  A word is (run length << 4) | code; words are in reading order (START -> END, the
+ * order of the rendered strings).  stats[8]: AT_CG_START_I / AT_CG_START_J (the end cell minus the rows / columns consumed: 0-based,
+ * inclusive), equal columns, unequal columns (both filled with either flavour), I bases, D bases, N bases, I runs + D runs.
+ * An op code above 3 or a walk below row / column 0 is an inconsistent list: ncigar = -1, a statistics row of -1, no word written.
+ */
+enum { AT_CIGAR_M = 1 };
+enum { AT_CG_START_I = 0, AT_CG_START_J = 1, AT_CG_EQUAL = 2, AT_CG_UNEQUAL = 3, AT_CG_INS = 4, AT_CG_DEL = 5, AT_CG_SKIP = 6,
+       AT_CG_GAPS = 7 };
+
+/* Host helper, the sibling of at_render: ops (END -> START) + end cell -> CIGAR words and statistics.  cigar may be NULL (counts and
+ * statistics only), else it needs nops words.  AT_ERR_DOMAIN for an inconsistent list (*ncigar = -1, stats all -1), AT_ERR_ARG for
+ * NULL / negative arguments.  No handle, no GPU. */
+int at_cigar(const uint8_t *ops, int32_t nops,
+             const uint8_t *s1, int32_t end_i, const uint8_t *s2, int32_t end_j, int flags,
+             uint32_t *cigar, int32_t *ncigar, int32_t stats[8]);
+
+/*
+ * The same on the GPU, from what at_align_batch_device left in HBM (arguments as at_render_batch_device): d_ncigar[k] runs and
+ * d_stats[k][8] (may be NULL) per pair, the exclusive prefix sums of the run counts in d_cigar_off[0 .. npairs]
+ * (d_cigar_off[npairs] = total words), pair k's words at d_cigar[d_cigar_off[k] ..).  Pairs that would end beyond cigar_cap are not
+ * written and no other word of d_cigar is touched: compare the total with the capacity.  A pair with d_nops[k] < 0 or an
+ * inconsistent list gets d_ncigar[k] = -1 and a statistics row of -1 and counts as 0 words.  npairs == 0 writes d_cigar_off[0] = 0
+ * only.  Asynchronous on `stream`.
+ */
+int at_cigar_batch_device(at_handle *h, int64_t npairs,
+                          const uint32_t *d_seq, int bits,
+                          const int64_t *d_woff1, const int64_t *d_woff2,
+                          const int32_t *d_end_i, const int32_t *d_end_j,
+                          const uint8_t *d_ops, const int64_t *d_ops_off, const int32_t *d_nops,
+                          int flags, int32_t *d_ncigar, int32_t *d_stats, int64_t *d_cigar_off,
+                          uint32_t *d_cigar, int64_t cigar_cap, void *stream);
+
+/*
+ * at_align_batch with CIGARs made on the GPU: neither op codes nor strings cross the link, only the fixed-size results, the
+ * statistics rows (out_stats[k][8]) and the packed words.  out_ncigar[k] runs per pair, out_cigar_off[0 .. npairs] their exclusive
+ * prefix sums in pair order (out_cigar_off[npairs] = total words): both always complete.  out_cigar receives the words of the pairs
+ * that end within cigar_cap; a caller whose buffer was too small compares the total with it and calls again.  Not for AT_MODE_EDIT.
+ */
+int at_align_batch_cigar(at_handle *h, int mode, int64_t npairs,
+                         const uint8_t *seq_blob,
+                         const int64_t *off1, const int32_t *len1,
+                         const int64_t *off2, const int32_t *len2,
+                         int flags,
+                         int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state,
+                         int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
+                         uint32_t *out_cigar, int64_t cigar_cap);
+
+/*
  * Multi-process batches: one process per GPU, each with its own handle.  The pairs are independent, so
  * the only communication is a broadcast of rank 0's scoring block and a gather of results, both RCCL collectives on the
  * handles' devices (over xGMI inside a node).  `dir` is a directory all ranks can reach: rank 0 leaves the RCCL id there.
