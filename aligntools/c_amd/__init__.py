@@ -28,7 +28,7 @@ ERR_ARG, ERR_DOMAIN = -1, -4
 ST_LOW, ST_MID, ST_UPP = 1, 2, 3
 
 # every symbol include/aligntools_hip.h declares
-ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_align_batch",
+ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_set_edit_traceback", "at_align_batch",
                "at_align_batch_device", "at_align_allpairs_device", "at_render_batch_device", "at_compact_ops_device",
                "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream", "at_search",
                "at_search_strands", "at_revcomp", "at_revcomp_device",
@@ -96,6 +96,8 @@ def load_library():
     lib.at_set_scoring.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_int), C.c_int]
     lib.at_set_min_score.restype = C.c_int
     lib.at_set_min_score.argtypes = [C.c_void_p, C.c_int, C.c_int32]
+    lib.at_set_edit_traceback.restype = C.c_int
+    lib.at_set_edit_traceback.argtypes = [C.c_void_p, C.c_int]
     lib.at_align_batch.restype = C.c_int
     lib.at_align_batch.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -260,6 +262,7 @@ class Aligner:
     def __init__(self, device=None):
         self._lib = load_library()
         self._h = C.c_void_p()
+        self._edit_tb = False
         ids = None if device is None else (C.c_int * 1)(int(device))
         rc = self._lib.at_init(ids, 1 if device is not None else 0, C.byref(self._h))
         if rc:
@@ -296,6 +299,13 @@ class Aligner:
         """All-vs-all overlap scores: pairs proven to score below `min_score` are not swept (state 0, score = an upper bound);
         None switches the threshold off (at_set_min_score)."""
         self._check(self._lib.at_set_min_score(self._h, 0 if min_score is None else 1, 0 if min_score is None else int(min_score)))
+
+    def set_edit_traceback(self, on=True):
+        """Edit alignments (at_set_edit_traceback): with it on, align_batch("edit", ...) returns `ops` (and r1 / r2 with render),
+        and align_batch_strings / align_batch_cigar accept "edit".  Needs u == 1, pure ACGT, first sequences of up to 1 024 and
+        second ones of up to 3 792 bases; outside that domain the calls raise.  Off (the default): edit returns the number only."""
+        self._check(self._lib.at_set_edit_traceback(self._h, 1 if on else 0))
+        self._edit_tb = bool(on)
 
     def align_batch_strings(self, mode, pairs):
         """pairs: list of (s1, s2) bytes/str.  The two gapped strings of every pair, rendered on the GPU
@@ -373,7 +383,7 @@ class Aligner:
         pairs = [(_b(a), _b(b)) for a, b in pairs]
         n = len(pairs)
         blob, off1, len1, off2, len2 = _flatten(pairs)
-        tb = bool(traceback) and mode != MODE_EDIT
+        tb = bool(traceback) and (mode != MODE_EDIT or getattr(self, "_edit_tb", False))
         score = np.zeros(n, dtype=np.int32)
         end_i = np.zeros(n, dtype=np.int32)
         end_j = np.zeros(n, dtype=np.int32)

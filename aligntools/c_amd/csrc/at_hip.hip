@@ -11,6 +11,7 @@
 #include "at_search.hip.h"
 #include "at_revcomp.hip.h"
 #include "at_cigar.hip.h"
+#include "at_edit_tb.hip.h"
 #include "../../../include/aligntools_hip.h"
 
 #include <algorithm>
@@ -93,6 +94,7 @@ struct at_handle {
 	int m = 1, u = -2, o = -5, e = -1, j = -10, use_jump = 0;
 	std::vector<int> sites;
 	int min_on = 0, min_score = 0;  /* at_set_min_score: all-vs-all overlap scores skip pairs proven below it */
+	int edit_tb = 0;                /* at_set_edit_traceback: edit batches with want_traceback deliver their ops (at_edit_tb.hip.h) */
 	/* device scratch (grow-only) */
 	uint32_t *d_sitemask = nullptr; size_t sitemask_words = 0; int sitemask_for_l2 = -1; bool sitemask_dirty = true;
 	uint32_t *d_ws = nullptr; size_t ws_bytes = 0;
@@ -273,6 +275,13 @@ extern "C" int at_set_min_score(at_handle *h, int enabled, int32_t min_score)
 	if (!h) return fail(nullptr, AT_ERR_ARG, "at_set_min_score: NULL handle");
 	h->min_on = enabled ? 1 : 0;
 	h->min_score = min_score;
+	return AT_OK;
+}
+
+extern "C" int at_set_edit_traceback(at_handle *h, int enabled)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_set_edit_traceback: NULL handle");
+	h->edit_tb = enabled ? 1 : 0;
 	return AT_OK;
 }
 
@@ -960,8 +969,10 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 	if (bits != 2 && bits != 8) return fail(h, AT_ERR_ARG, "bits must be 2 or 8");
 	if (npairs == 0) return AT_OK;
 	if (!d_seq || !d_woff1 || !d_len1 || !d_woff2 || !d_len2 || !d_score) return fail(h, AT_ERR_ARG, "NULL device pointer");
+	/* edit alignments (at_set_edit_traceback): batches only -- the all-pairs entries keep the number */
+	const bool edit_tb = want_traceback && mode == AT_MODE_EDIT && h->edit_tb && ap_n == 0;
 	const bool tb = want_traceback && mode != AT_MODE_EDIT;
-	if (tb && (!d_ops || !d_ops_off || !d_nops)) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
+	if ((tb || edit_tb) && (!d_ops || !d_ops_off || !d_nops)) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
 	hipStream_t stream = (hipStream_t)stream_;
 	HIP_TRY(h, hipSetDevice(h->device));
 	drop_stale_error();
@@ -1253,6 +1264,51 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		return AT_OK;
 	}
 
+	/* ---- edit alignments (at_set_edit_traceback): the bit-parallel fill keeps its columns, the same wavefront walks them
+	 * (at_edit_tb.hip.h).  Outside the domain the call fails: no silent fall back to the number alone ---- */
+	if (edit_tb) {
+		const size_t lds = 64 * ((((size_t)max_len2 + 15) / 16 + 2) | 1) * 4;   /* the 64 s2 windows of a wavefront (odd stride, as the kernel computes it) */
+		if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "edit alignments need the unit mismatch cost: u = %d, not 1", h->u);
+		if (bits != 2) return fail(h, AT_ERR_DOMAIN, "edit alignments need a 2-bit batch: some base is not one of ACGT");
+		if (max_len1 > 1024) return fail(h, AT_ERR_DOMAIN, "edit alignments: max_len1 = %d exceeds 1024", max_len1);
+		if (lds > 60 * 1024) return fail(h, AT_ERR_DOMAIN, "edit alignments: max_len2 = %d exceeds 3792 (64 windows of packed words in 60 KB of LDS)", max_len2);
+		const int w = max_len1 <= 64 ? 2 : max_len1 <= 96 ? 3 : max_len1 <= 128 ? 4 : max_len1 <= 160 ? 5 : max_len1 <= 256 ? 8 : max_len1 <= 512 ? 16 : 32;
+		at_edit_tb_fn fn = at_pick_edit_tb(w);
+		if (!fn) return fail(h, AT_ERR_ARG, "no edit alignment kernel for %d words per lane", w);
+		/* the slab: one column is W words x 2 planes x 64 lanes; bounded like the pointer slots of plan_launch */
+		const long long slab_words = (long long)std::max(max_len2, 1) * w * 128;
+		const long long cap = env_ll("AT_WS_CAP_MB", 16384) << 20;
+		if (slab_words * 4 > cap)
+			return fail(h, AT_ERR_NOMEM, "edit alignments: one work item needs %lld workspace bytes (cap %lld)", slab_words * 4, cap);
+		int occ = 0;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, 64, lds) != hipSuccess || occ <= 0) occ = 8;
+		const long long per_cu = std::max(1LL, std::min<long long>(occ, env_ll("AT_WAVES_PER_CU", 16)));
+		const long long grid = std::max(1LL, std::min<long long>(std::min<long long>((npairs + 63) / 64, per_cu * h->ncu), cap / (slab_words * 4)));
+		{
+			void *p = h->d_ws; size_t have = h->ws_bytes;
+			int rc = grow(h, &p, &have, (size_t)(grid * slab_words * 4), "ws");
+			h->d_ws = (uint32_t *)p; h->ws_bytes = have;
+			if (rc) return rc;
+		}
+		at::EditTbArgs ea;
+		memset(&ea, 0, sizeof ea);
+		ea.m.npairs = npairs; ea.m.seq = d_seq;
+		ea.m.woff1 = (const long long *)d_woff1; ea.m.woff2 = (const long long *)d_woff2; ea.m.len1 = d_len1; ea.m.len2 = d_len2;
+		ea.m.max_l1 = max_len1; ea.m.max_l2 = max_len2;
+		ea.m.score = d_score; ea.m.end_i = d_end_i; ea.m.end_j = d_end_j; ea.m.state = d_state; ea.m.nops = d_nops;
+		ea.m.order = d_order;
+		ea.ops = d_ops; ea.ops_off = (const long long *)d_ops_off;
+		ea.slab = h->d_ws; ea.slab_words = slab_words;
+		if (!h->d_queue) { HIP_TRY(h, hipMalloc((void **)&h->d_queue, 128)); HIP_TRY(h, hipMemset(h->d_queue, 0, 128)); }
+		HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, 8, stream));
+		ea.m.queue = h->d_queue;
+		hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, stream, ea);
+		HIP_TRY(h, hipGetLastError());
+		snprintf(h->cfg, sizeof h->cfg, "myers-tb bits=2 words/lane=%d (64 pairs/wave) lds=%zuB slab=%lldB waves/cu<=%lld grid=%lld", w, lds,
+		         slab_words * 4, per_cu, grid);
+		return AT_OK;
+	}
+
 	/* ---- edit distance with unit mismatch cost: bit-parallel kernel (at_myers.hip.h), any mix of lengths ---- */
 	/* (bytes of LDS for the s2 windows of the n alignments of a wavefront; two must fit, or the cell-by-cell kernel takes the batch) */
 	auto myers_windows = [&](int n) { return (size_t)n * ((((size_t)max_len2 + 15) / 16 + 2) | 1) * 4; };
@@ -1455,7 +1511,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	if (npairs < 0) return fail(h, AT_ERR_ARG, "negative npairs");
 	if (npairs == 0) return AT_OK;
 	if (!seq_blob || !off1 || !len1 || !off2 || !len2 || !out_score) return fail(h, AT_ERR_ARG, "NULL argument");
-	const bool tb = want_traceback && mode != AT_MODE_EDIT;
+	const bool tb = want_traceback && (mode != AT_MODE_EDIT || h->edit_tb);
 	const bool strings = out_r1 != nullptr, cigar = cg != nullptr;
 	if (tb && ((!out_ops && !strings && !cigar) || !ops_off || !out_nops)) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
 
@@ -1993,6 +2049,7 @@ static int align_host_mt(at_handle *h, int mode, int64_t npairs, const uint8_t *
 	}
 	for (int c = 0; c < nchunks - 1; ++c) {
 		at_handle *k = h->kids[(size_t)c];
+		k->edit_tb = h->edit_tb;
 		if (k->m != h->m || k->u != h->u || k->o != h->o || k->e != h->e || k->j != h->j || k->use_jump != h->use_jump ||
 		    k->sites != h->sites) {
 			k->m = h->m; k->u = h->u; k->o = h->o; k->e = h->e; k->j = h->j; k->use_jump = h->use_jump; k->sites = h->sites;
@@ -2537,7 +2594,7 @@ extern "C" int at_align_batch_strings(at_handle *h, int mode, int64_t npairs, co
                                       int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state,
                                       char *out_r1, char *out_r2, const int64_t *str_off, int32_t *out_len)
 {
-	if (mode == AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "edit has no alignment strings (alignment.h:291)");
+	if (mode == AT_MODE_EDIT && !(h && h->edit_tb)) return fail(h, AT_ERR_ARG, "edit has no alignment strings (alignment.h:291)");
 	if (!out_r1 || !out_r2 || !str_off || !out_len) return fail(h, AT_ERR_ARG, "NULL string buffers");
 	return guarded(h, "at_align_batch_strings", [&] {
 		return align_host_mt(h, mode, npairs, seq_blob, off1, len1, off2, len2, 1, out_score, out_end_i, out_end_j, out_state,
@@ -2553,7 +2610,7 @@ extern "C" int at_align_batch_cigar(at_handle *h, int mode, int64_t npairs, cons
                                     uint32_t *out_cigar, int64_t cigar_cap)
 {
 	if (!h) return fail(nullptr, AT_ERR_ARG, "at_align_batch_cigar: NULL handle");
-	if (mode == AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "edit has no alignment, hence no CIGAR (alignment.h:291)");
+	if (mode == AT_MODE_EDIT && !h->edit_tb) return fail(h, AT_ERR_ARG, "edit has no alignment, hence no CIGAR (alignment.h:291)");
 	if (npairs < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "negative size");
 	if (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)) return fail(h, AT_ERR_ARG, "NULL CIGAR buffers");
 	if (npairs == 0) { out_cigar_off[0] = 0; return AT_OK; }

@@ -10,6 +10,8 @@
  *   alignTools batch <command> [options] --queries <queries.fa> [--best K] [--both-strands] <targets.fa>
  *     every query against every target; the best K hits of each query are printed.
  *   ... --paf (both forms, not edit): one PAF line per pair / hit (at_align_batch_cigar) instead of the name line and two strings.
+ *   ... edit -u 1 --alignments (both forms): the alignment behind every distance (at_set_edit_traceback) -- the record the other four
+ *       commands print, or with --paf its PAF line.
  */
 #define _POSIX_C_SOURCE 200809L
 #include "at_host.h"
@@ -138,9 +140,13 @@ static int main_single(int cmd, int argc, char *argv[])
  *                    --both-strands also searches every query's reverse complement (at_search_strands; made on the GPU): a hit's
  *                    header line gets a fourth column, + or -, and the strings of a - hit are those of the reverse-complemented
  *                    query; ties on score and target: + first.
- *     --paf          one PAF line per pair / hit instead of the name line and the two strings: the twelve columns (mapq 255), AS:i,
+ *     --paf          one PAF line per pair / hit instead of the name line and the two strings: the twelve columns (mapq 255), AS:i (edit: minus the distance),
  *                    NM:i and cg:Z with the =/X CIGAR, from at_align_batch_cigar -- statistics rows and CIGAR words come down, no
  *                    strings.  A - hit of --both-strands has its query coordinates on the query as given.  Not for edit,
+ *                    --score-only, --all-vs-all, --gpus N > 1.
+ *     --alignments   (edit -u 1) the alignment behind every distance (at_set_edit_traceback): the name line with edit_distance=%d and
+ *                    the two gapped strings, like the other four commands; with --paf the PAF line -- NM:i is the distance, AS:i
+ *                    minus the distance (higher stays better), cg:Z the =/X CIGAR.  Also on the hit pairs of --queries.  Not with
  *                    --score-only, --all-vs-all, --gpus N > 1.
  *     --gpus N       one process per GPU: this process starts N workers (itself, with AT_RANK / AT_WORLD / AT_DEVICE /
  *                    AT_COMM_DIR in their environment), rank 0's options are broadcast over RCCL, every rank aligns a
@@ -150,7 +156,8 @@ static int main_single(int cmd, int argc, char *argv[])
  * thread -- which also pays the HIP start-up, in the shadow of the first chunks' parsing -- sends each chunk to the GPU
  * and writes its results with one fwrite.  Memory is bounded by the chunks in flight, whatever the size of the file;
  * --all-vs-all keeps the read set and streams slices of the triangle instead (at_align_allpairs_stream). */
-typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf; } batch_flags;
+typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments; } batch_flags;
+static int g_edit_alignments;   /* --alignments: every handle of this process delivers edit alignments (set before any handle exists) */
 
 /* linear index p of the strict upper triangle of n x n (row-major) -> (a, b), a < b: closed form + integer correction */
 static void tri_seek(int64_t p, int64_t n, int64_t *a, int64_t *b)
@@ -361,6 +368,7 @@ static void *pipe_consumer(void *arg)
 	tbuf out = {NULL, 0, 0};
 	const opt_t *opt = pp->opt;
 	int rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, opt->s == AT_TRUE, opt->sites.pos, (int)opt->sites.size);
+	if (rc == AT_OK && g_edit_alignments) rc = at_set_edit_traceback(h, 1);
 	if (rc != AT_OK) die("%s", at_last_error(h));
 	memset(&w, 0, sizeof w);
 	w.paf = pp->paf;
@@ -383,7 +391,8 @@ static void *pipe_consumer(void *arg)
 		trace("chunk aligned, pairs", n);
 		for (k = 0; k < n; ++k)
 			if (pp->paf)
-				tb_paf(&out, c->names + c->name_off[2 * k], w.l1[k], '+', c->names + c->name_off[2 * k + 1], w.l2[k], w.score[k], w.ei[k], w.ej[k],
+				tb_paf(&out, c->names + c->name_off[2 * k], w.l1[k], '+', c->names + c->name_off[2 * k + 1], w.l2[k],
+				       pp->cmd == C_EDIT ? -w.score[k] : w.score[k], w.ei[k], w.ej[k],
 				       w.stats + 8 * k, w.cg + w.cgoff[k], w.ncg[k]);
 			else
 				tb_pair(&out, c->names + c->name_off[2 * k], c->names + c->name_off[2 * k + 1], w.score[k], pp->cmd == C_EDIT,
@@ -488,7 +497,7 @@ static int batch_worker(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	int64_t nrec, npairs, lo, hi, a = 0, b = 0;
 	int64_t *roff = NULL;
 	int32_t *rlen = NULL;
-	const int tb = !bf->score_only && cmd != C_EDIT;
+	const int tb = !bf->score_only && (cmd != C_EDIT || bf->alignments);
 	const int comm = world > 1 || getenv("AT_COMM_FORCE_RCCL") != NULL;   /* (the latter: the RCCL calls at world size 1, for tests) */
 	const int mode = cmd == C_GLOBAL ? AT_MODE_GLOBAL : cmd == C_LOCAL ? AT_MODE_LOCAL : cmd == C_FIT ? AT_MODE_FIT
 	               : cmd == C_OVERLAP ? AT_MODE_OVERLAP : AT_MODE_EDIT;
@@ -521,6 +530,7 @@ static int batch_worker(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	if (hi > npairs) hi = npairs;
 	h = at_host_handle();
 	rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, opt->s == AT_TRUE, opt->sites.pos, (int)opt->sites.size);
+	if (rc == AT_OK && g_edit_alignments) rc = at_set_edit_traceback(h, 1);
 	if (rc == AT_OK && comm) {
 		trace("comm: init, rank", rank);
 		rc = at_comm_init(h, rank, world, comm_dir);
@@ -652,7 +662,7 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	int32_t *qlen, *tlen, *tgt, *sc, *ei, *ej, *st, *nh, *sd = NULL;
 	uint8_t *blob2 = NULL;
 	int rc, j;
-	const int tb = !bf->score_only && cmd != C_EDIT, kb = bf->best;
+	const int tb = !bf->score_only && (cmd != C_EDIT || bf->alignments), kb = bf->best;
 	const int mode = cmd == C_GLOBAL ? AT_MODE_GLOBAL : cmd == C_LOCAL ? AT_MODE_LOCAL : cmd == C_FIT ? AT_MODE_FIT
 	               : cmd == C_OVERLAP ? AT_MODE_OVERLAP : AT_MODE_EDIT;
 	if (!rq) die("Can't open %s\n", qfile);
@@ -672,6 +682,7 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	if (nq == 0 || nt == 0) { at_chunk_free(&c); return 0; }
 	h = at_host_handle();
 	rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, opt->s == AT_TRUE, opt->sites.pos, (int)opt->sites.size);
+	if (rc == AT_OK && g_edit_alignments) rc = at_set_edit_traceback(h, 1);
 	if (rc != AT_OK) die("%s", at_last_error(h));
 	qoff = (int64_t *)at_xmalloc((size_t)nq * 8); qlen = (int32_t *)at_xmalloc((size_t)nq * 4);
 	toff = (int64_t *)at_xmalloc((size_t)nt * 8); tlen = (int32_t *)at_xmalloc((size_t)nt * 4);
@@ -730,7 +741,7 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 		for (j = 0; j < nh[q]; ++j, ++x)
 			if (bf->paf)
 				tb_paf(&out, c.names + c.name_off[q], qlen[q], sd && sd[q * kb + j] == 1 ? '-' : '+', c.names + c.name_off[nq + tgt[q * kb + j]],
-				       tlen[tgt[q * kb + j]], w.score[x], w.ei[x], w.ej[x], w.stats + 8 * x, w.cg + w.cgoff[x], w.ncg[x]);
+				       tlen[tgt[q * kb + j]], cmd == C_EDIT ? -w.score[x] : w.score[x], w.ei[x], w.ej[x], w.stats + 8 * x, w.cg + w.cgoff[x], w.ncg[x]);
 			else
 				tb_pair_strand(&out, c.names + c.name_off[q], c.names + c.name_off[nq + tgt[q * kb + j]], sc[q * kb + j], cmd == C_EDIT,
 				        sd ? (sd[q * kb + j] == 1 ? '-' : '+') : 0, tb ? w.r1 + w.slot[x] : NULL, tb ? w.r2 + w.slot[x] : NULL, tb ? (size_t)w.nops[x] : 0);
@@ -803,10 +814,10 @@ static int main_batch(int argc, char *argv[], char *argv0)
 {
 	int cmd = -1, k, n = 0;
 	opt_t *opt = init_opt();
-	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0};
+	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0};
 	char **av = (char **)at_xmalloc((size_t)(argc + 1) * sizeof(char *));
-	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] [--paf] <pairs.fa>\n"
-	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] <targets.fa>\n";
+	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] [--paf] [--alignments] <pairs.fa>\n"
+	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] <targets.fa>\n";
 	/* the long flags of the extension are taken out before getopt sees the reference's short options */
 	for (k = 0; k < argc; ++k) {
 		if (strcmp(argv[k], "--score-only") == 0) bf.score_only = 1;
@@ -817,6 +828,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (strcmp(argv[k], "--best") == 0 && k + 1 < argc) { bf.best = atoi(argv[++k]); bf.best_set = 1; }
 		else if (strcmp(argv[k], "--both-strands") == 0) bf.both = 1;
 		else if (strcmp(argv[k], "--paf") == 0) bf.paf = 1;
+		else if (strcmp(argv[k], "--alignments") == 0) bf.alignments = 1;
 		else av[n++] = argv[k];
 	}
 	av[n] = NULL;
@@ -832,7 +844,11 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (bf.best_set && !bf.queries) why = "--best goes with --queries";
 		else if (bf.both && !bf.queries) why = "--both-strands goes with --queries";
 		else if (bf.queries && (bf.best < 1 || bf.best > 64)) why = "--best K needs 1 <= K <= 64";
-		else if (bf.paf && cmd == C_EDIT) why = "--paf does not go with edit (edit has no alignment)";
+		else if (bf.alignments && cmd != C_EDIT) why = "--alignments goes with edit";
+		else if (bf.alignments && bf.score_only) why = "--alignments does not go with --score-only";
+		else if (bf.alignments && bf.all_vs_all) why = "--alignments does not go with --all-vs-all";
+		else if (bf.alignments && bf.gpus > 1) why = "--alignments runs on one GPU: it does not go with --gpus N > 1";
+		else if (bf.paf && cmd == C_EDIT && !bf.alignments) why = "--paf does not go with edit (edit has no alignment)";
 		else if (bf.paf && bf.score_only) why = "--paf does not go with --score-only (a PAF line needs the traceback)";
 		else if (bf.paf && bf.all_vs_all) why = "--paf does not go with --all-vs-all";
 		else if (bf.paf && bf.gpus > 1) why = "--paf runs on one GPU: it does not go with --gpus N > 1";
@@ -843,6 +859,8 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	}
 	if (parse_opts(cmd, n - 1, av + 1, opt)) { free(opt); free(av); return 1; }
 	if (optind + 1 > n - 1) { cmd_usage(cmd, opt); free(opt); free(av); return 1; }
+	if (bf.alignments && opt->u != 1) { fprintf(stderr, "--alignments needs -u 1\n%s", usage_line); free(opt); free(av); return 1; }
+	g_edit_alignments = bf.alignments;
 	if (bf.queries) {
 		k = batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
 		free(opt->sites.pos); free(opt); free(av);

@@ -171,6 +171,30 @@ int at_align_allpairs(at_handle *h, int mode, int64_t nreads,
 int at_set_min_score(at_handle *h, int enabled, int32_t min_score);
 
 /*
+ * Edit ALIGNMENTS: the alignment behind the number AT_MODE_EDIT returns.  A per-handle setting; enabled = 0 (the default) changes
+ * nothing anywhere.  The reference's edit_dist (alignment.h:291-315) has no traceback, so the rule is this library's.  D is its table
+ * with the unit mismatch cost: D(i,0) = i, D(0,j) = j, D(i,j) = min(D(i,j-1) + 1, D(i-1,j-1) + (s1[i-1] != s2[j-1]), D(i-1,j) + 1).
+ * The op list runs END -> START like every other mode's, from (l1, l2) to (0, 0); at cell (i, j) the first rule that holds:
+ *   1. i > 0 && j > 0 && D(i-1,j-1) + (s1[i-1] != s2[j-1]) == D(i,j)    AT_OP_MID, i--, j--
+ *   2. i > 0 && D(i-1,j) + 1 == D(i,j)                                  AT_OP_LOW, i--
+ *   3. otherwise                                                        AT_OP_UPP, j--
+ * score = D(l1,l2), end cell (l1, l2), state AT_ST_MID (what the number-only path returns), nops <= l1 + l2; the number of mismatch
+ * columns plus gap columns equals the score.
+ * With the setting on
+ *   - at_align_batch and at_align_batch_device with AT_MODE_EDIT and want_traceback != 0 deliver the ops in the usual slots (exactly
+ *     nops bytes written, nothing else touched); with want_traceback == 0 they take the number-only route as before;
+ *   - at_align_batch_strings and at_align_batch_cigar accept AT_MODE_EDIT and run the rendering / CIGAR kernels over those ops.
+ * The domain: mismatch cost u == 1, a 2-bit (pure ACGT) batch, max_len1 <= 1 024, and max_len2 no longer than 64 windows of packed
+ * words hold in 60 KB of LDS (3 792 bases).  Outside it the call fails with AT_ERR_DOMAIN and a text that names the broken bound;
+ * there is no silent fall back to the number alone.  The fill keeps two words per 32 rows and column in the handle's workspace
+ * (max_len2 * W * 512 bytes per wavefront of 64 pairs, W = 2 .. 32 words for reads of up to 64 .. 1 024 bases), bounded like the
+ * pointer slots of the sweeps; a work item above that bound is AT_ERR_NOMEM.
+ * Edit stays number-only, whatever the setting, in the all-pairs entries and in the searches, for 8-bit alphabets, reads beyond
+ * 1 024 bases, u != 1, multi-GPU batches and the reference-named single-pair surface of aligntools.h.
+ */
+int at_set_edit_traceback(at_handle *h, int enabled);
+
+/*
  * The same sweep with bounded memory, for triangles too large to hold (C5: 50 000 reads = 1.25e9 pairs = 20 GB of
  * results): scores and end cells only, the triangle cut into slices of at most chunk_pairs pairs (<= 0: 4 Mi); `fn`
  * is called once per slice, in pair order, on the calling thread, while the GPU already sweeps the next slice.  The
@@ -273,7 +297,7 @@ int at_compact_ops_device(at_handle *h, int64_t npairs,
 /*
  * at_align_batch with the rendering done on the GPU: instead of op codes the caller receives the reference's
  * two strings per pair (0-terminated) at out_r1/out_r2 + str_off[k], slots of len1[k]+len2[k]+1 bytes, and
- * their common length in out_len[k].  Not for AT_MODE_EDIT (edit_dist returns a number only).
+ * their common length in out_len[k].  AT_MODE_EDIT only with at_set_edit_traceback on (edit_dist returns a number only).
  */
 int at_align_batch_strings(at_handle *h, int mode, int64_t npairs,
                            const uint8_t *seq_blob,
@@ -322,7 +346,7 @@ int at_cigar_batch_device(at_handle *h, int64_t npairs,
  * at_align_batch with CIGARs made on the GPU: neither op codes nor strings cross the link, only the fixed-size results, the
  * statistics rows (out_stats[k][8]) and the packed words.  out_ncigar[k] runs per pair, out_cigar_off[0 .. npairs] their exclusive
  * prefix sums in pair order (out_cigar_off[npairs] = total words): both always complete.  out_cigar receives the words of the pairs
- * that end within cigar_cap; a caller whose buffer was too small compares the total with it and calls again.  Not for AT_MODE_EDIT.
+ * that end within cigar_cap; a caller whose buffer was too small compares the total with it and calls again.  AT_MODE_EDIT only with at_set_edit_traceback on.
  */
 int at_align_batch_cigar(at_handle *h, int mode, int64_t npairs,
                          const uint8_t *seq_blob,
