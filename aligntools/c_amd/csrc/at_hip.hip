@@ -5,6 +5,8 @@
  * compute path: every DP cell is computed on the GPU or the call fails.
  */
 #include "at_launch.h"
+#include "at_classes.h"
+#include "at_ragplan.h"
 #include "at_pack.hip.h"
 #include "at_render.hip.h"
 #include "at_myers.hip.h"
@@ -149,6 +151,16 @@ static int fail(at_handle *h, int code, const char *fmt, ...)
 	snprintf(g_err, sizeof g_err, "%s", buf);
 	if (h) snprintf(h->err, sizeof h->err, "%s", buf);
 	return code;
+}
+
+/* at_last_config grows by notes: what a later stage of the call did */
+__attribute__((format(printf, 2, 3))) static void cfg_append(at_handle *h, const char *fmt, ...)
+{
+	const size_t used = strlen(h->cfg);
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(h->cfg + used, sizeof h->cfg - used, fmt, ap);
+	va_end(ap);
 }
 
 /* no C++ exception crosses the C ABI (std::bad_alloc from a vector or a string on the host side): it becomes an error code */
@@ -481,7 +493,6 @@ static Layout layout_for(int kmode, int bits, bool tb, int max_l1, int max_l2)
 	return L;
 }
 
-
 /* The 2-bit kernels read scores from a signed-byte LUT: scaled match/mismatch (minus the gap for overlap) must fit. */
 static bool scores_fit_byte(const at_handle *h, int mode)
 {
@@ -532,31 +543,31 @@ static Layout16 layout16_for(bool tb, bool hasj, int l1, int l2, int ts, int for
 		/* ragged frames of reads of 305 .. 608 bases, or (force_k) the sliver behind a batch of narrow-group items: one strip on two
 		 * groups of 32 lanes */
 		L.g = 32;
-		L.k = force_k ? force_k : l1 <= 320 ? 10 : l1 <= 384 ? 12 : l1 <= 416 ? 13 : l1 <= 512 ? 16 : 19;
-	} else if (!force_g && (g_forced == 0 || g_forced == 4) && ts == 4 && l1 <= 76) {
+		L.k = force_k ? force_k : at::class_rows(at::kClass32, l1, at::kClass32RagFirst);
+	} else if (!force_g && (g_forced == 0 || g_forced == 4) && ts == 4 && l1 <= at::class_top(at::kClass4)) {
 		/* reads of up to 76 bases: sixteen groups of 4 lanes x 9 / 10 / 13 / 16 / 19 rows, 32 alignments per wave */
 		L.g = 4;
-		L.k = l1 <= 36 ? 9 : l1 <= 40 ? 10 : l1 <= 52 ? 13 : l1 <= 64 ? 16 : 19;
-	} else if (force_g != 16 && (force_g == 8 || g_forced == 0 || g_forced == 8) && ts == 4 && l1 <= 152) {
+		L.k = at::class_rows(at::kClass4, l1);
+	} else if (force_g != 16 && (force_g == 8 || g_forced == 0 || g_forced == 8) && ts == 4 && l1 <= at::class_top(at::kClass8)) {
 		L.g = 8;
-		L.k = l1 <= 40 ? 5 : l1 <= 48 ? 6 : l1 <= 56 ? 7 : l1 <= 64 ? 8 : l1 <= 80 ? 10 : l1 <= 104 ? 13 : l1 <= 128 ? 16 : 19;
+		L.k = at::class_rows(at::kClass8, l1);
 	} else if ((force_g == 16 || g_forced != 64) && ts == 4 && l1 <= 208) {
 		L.g = 16;
-		L.k = l1 <= 64 ? 4 : l1 <= 80 ? 5 : l1 <= 96 ? 6 : l1 <= 112 ? 7 : (l1 <= 160 ? 10 : 13);
-	} else if ((force_g == 16 || (!force_g && g_forced != 64 && g_forced != 32)) && ts == 4 && l1 > 208 && l1 <= 304) {
+		L.k = at::class_rows(at::kClass16, l1);
+	} else if ((force_g == 16 || (!force_g && g_forced != 64 && g_forced != 32)) && ts == 4 && l1 > 208 && l1 <= at::class_top(at::kClass16)) {
 		/* 250- and 300-base reads: still four groups of 16 lanes, 16 or 19 rows per lane (8 alignments per wave; AT_GROUP=32: the
 		 * two 32-lane groups below) */
 		L.g = 16;
-		L.k = l1 <= 256 ? 16 : 19;
+		L.k = at::class_rows(at::kClass16, l1);
 	} else if (g_forced != 64 && ts == 4 && l1 > 208 &&
-	           l1 <= (force_g || g_forced == 32 ? 416 : kmode == at::K_LOCAL ? 608 : kmode == at::K_GLOBAL ? 512 : 416)) {
+	           l1 <= (force_g || g_forced == 32 ? at::kTopFit : kmode == at::K_LOCAL ? at::kTopLocal : kmode == at::K_GLOBAL ? at::kTopGlobal : at::kTopFit)) {
 		/* 250- and 300-base reads: two groups of 32 lanes (4 alignments per wave); one group of 64 lanes would carry 2 and
 		 * cut 300 rows into a strip of 256 and one of 44 */
 		L.g = 32;
 		/* 305 .. 608 bases: still one strip -- 10, 12, 13, 16 or 19 rows per lane (AT_GROUP=32: the round-1 classes only, 417+ on the
 		 * 64-lane groups).  16 rows only for local and global, 19 only for local: the others spill there (268 .. 612 bytes of
 		 * scratch per lane) and lose to the strips of the 64-lane group (global 560 / 608 bases: -4 %) */
-		L.k = l1 <= 224 ? 7 : l1 <= 256 ? 8 : l1 <= 320 ? 10 : l1 <= 384 && g_forced != 32 ? 12 : l1 <= 416 ? 13 : l1 <= 512 ? 16 : 19;
+		L.k = at::class_rows(at::kClass32, l1, 0, g_forced == 32 ? at::kClass32SkipUnderGroup32 : 0);
 	}
 	const int ng = 64 / L.g;
 	const int blk = L.g <= 16 ? 4 : 8;        /* BLK of at_sweep16 */
@@ -725,7 +736,13 @@ static int ensure_sitemask(at_handle *h, int max_l2, hipStream_t stream)
 	return AT_OK;
 }
 
-
+/* the handle's work counter block (128 bytes, zeroed when it is made); every launch starts with its work counter at zero */
+static int ensure_queue(at_handle *h, hipStream_t stream)
+{
+	if (!h->d_queue) { HIP_TRY(h, hipMalloc((void **)&h->d_queue, 128)); HIP_TRY(h, hipMemset(h->d_queue, 0, 128)); }
+	HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, 8, stream));
+	return AT_OK;
+}
 
 /* Storage class + grid for one launch.
  *   store 0  s2 window, boundary row and pointer matrix in LDS
@@ -797,8 +814,7 @@ static int plan_launch(at_handle *h, const char *tag, int k, long long nwork, lo
 		pl->ws = h->d_ws;
 	}
 	pl->grid = grid;
-	if (!h->d_queue) { HIP_TRY(h, hipMalloc((void **)&h->d_queue, 128)); HIP_TRY(h, hipMemset(h->d_queue, 0, 128)); }
-	HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, 8, stream));
+	if (int rcq = ensure_queue(h, stream)) return rcq;
 	static const char *names[3] = {"lds", "lds+hbm-pointers", "hbm"};
 	snprintf(h->cfg, sizeof h->cfg, "%s store=%s rows/lane=%d lds=%zuB slot=%lldB waves/cu<=%lld grid=%lld", tag, names[store], k,
 	         pl->dyn_lds, slot_words * 4, per_cu, grid);
@@ -1021,17 +1037,18 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		/* overlap: the packed kernel exists with pointers only (scores alone: the int32 kernel's 2 instructions per cell win) */
 		if (kmode == at::K_OVERLAP && (!tb || getenv("AT_NO_PACKED_OVERLAP"))) ts = 0;
 	}
-	if (rag && (!ts || (kmode > at::K_FITJ && !(kmode == at::K_OVERLAP && rag == 64)) || max_len1 > (rag == 8 ? 152 : rag == 16 ? 304 : rag == 32 ? 608 : 1024) || !d_order))
+	if (rag && (!ts || (kmode > at::K_FITJ && !(kmode == at::K_OVERLAP && rag == 64)) || max_len1 > at::rag_group_top(rag) || !d_order))
 		return fail(h, AT_ERR_ARG, "ragged packed launch outside its domain");   /* the host entry checks before it asks */
 	Layout16 P;
 	if (ts) {
 		P = layout16_for(tb, kmode == at::K_FITJ, max_len1, max_len2, ts, rag, kmode == at::K_OVERLAP, kmode,
-		                 rag && kmode == at::K_OVERLAP ? (max_len1 <= 256 ? 4 : 16) : 0);   /* (ragged overlap: one strip) */
+		                 rag && kmode == at::K_OVERLAP ? at::class_rows(at::kClassOvl, max_len1) : 0);   /* (ragged overlap: one strip) */
 		/* A 64-lane packed wave carries 2 alignments where an int32 wave carries 1: fewer, longer work items.  A batch
 		 * that cannot give every resident wave one of them stays on the int32 kernel.  (10k x 1024^2 = 1.6 rounds: 1.96
-		 * packed vs 2.00 TCUPS int32 for a lone launch, 2.70 vs 2.13 with launches in flight; 61k pairs: 2.70 vs 2.19.) */
+		 * packed vs 2.00 TCUPS int32 for a lone launch, 2.70 vs 2.13 with launches in flight; 61k pairs: 2.70 vs 2.19.)  Not a ragged launch:
+		 * its order is padded with ~index repeats, which only the packed kernels understand */
 		const double min_rounds = getenv("AT_PACKED_MIN_ROUNDS") ? atof(getenv("AT_PACKED_MIN_ROUNDS")) : 1.0;
-		if (P.g == 64 && (double)((npairs + 1) / 2) < min_rounds * 12.0 * h->ncu) ts = 0;
+		if (!rag && P.g == 64 && (double)((npairs + 1) / 2) < min_rounds * 12.0 * h->ncu) ts = 0;
 		/* the packed kernels index their slot with 24-bit multiplies: a pair whose slot would not fit takes the int32 kernel */
 		if (P.words >= (1LL << 24)) { if (rag) return fail(h, AT_ERR_ARG, "ragged packed launch outside its domain (slot too large)"); ts = 0; }
 		/* no packed kernel for the storage class this shape needs (the 16- and 32-lane groups have no all-HBM variant:
@@ -1165,7 +1182,7 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			const long long rsv = env_ll("AT_TP_RESERVE", 0) * h->ncu;
 			if (rsv > 0 && pl.grid > rsv && nwork > pl.grid - rsv) {
 				pl.grid = std::max<long long>(h->ncu, pl.grid - rsv);
-				snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " (AT_TP_RESERVE: sweep grid=%lld)", pl.grid);
+				cfg_append(h, " (AT_TP_RESERVE: sweep grid=%lld)", pl.grid);
 			}
 		}
 		int64_t n_tail = 0;
@@ -1250,29 +1267,29 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			/* (the main alignments' walker wavefronts: with fewer than one per 128 alignments, they refill from the counters) */
 			char wnote[128];
 			snprintf(wnote, sizeof wnote, " [walkers: %lld wavefronts%s for %lld alignments]", teams ? wteams : wmain, teams ? " of teams" : "", (long long)nm);
-			snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), "%s", wnote);
+			cfg_append(h, "%s", wnote);
 			walk_last = wnote;
 			HIP_TRY(h, hipGetLastError());
 		}
 		if (n_tail > 0)
-			snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " + last %lld pairs as 32-lane items (rows/lane=%d)", (long long)n_tail, PT.k);
+			cfg_append(h, " + last %lld pairs as 32-lane items (rows/lane=%d)", (long long)n_tail, PT.k);
 		if (first == 0) cfg_first = h->cfg;
 		}
 		if (piece < npairs) snprintf(h->cfg, sizeof h->cfg, "%.360s; in pieces of %lld pairs%s%s", cfg_first.c_str(), (long long)piece,
 		                              walk_last.empty() ? "" : "; last piece", walk_last.c_str());
-		if (ck_note[0]) snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), "%s", ck_note);
+		if (ck_note[0]) cfg_append(h, "%s", ck_note);
 		return AT_OK;
 	}
 
 	/* ---- edit alignments (at_set_edit_traceback): the bit-parallel fill keeps its columns, the same wavefront walks them
 	 * (at_edit_tb.hip.h).  Outside the domain the call fails: no silent fall back to the number alone ---- */
 	if (edit_tb) {
-		const size_t lds = 64 * ((((size_t)max_len2 + 15) / 16 + 2) | 1) * 4;   /* the 64 s2 windows of a wavefront (odd stride, as the kernel computes it) */
+		const size_t lds = at::myers_window_bytes(64, max_len2);   /* the 64 s2 windows of a wavefront */
 		if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "edit alignments need the unit mismatch cost: u = %d, not 1", h->u);
 		if (bits != 2) return fail(h, AT_ERR_DOMAIN, "edit alignments need a 2-bit batch: some base is not one of ACGT");
 		if (max_len1 > 1024) return fail(h, AT_ERR_DOMAIN, "edit alignments: max_len1 = %d exceeds 1024", max_len1);
 		if (lds > 60 * 1024) return fail(h, AT_ERR_DOMAIN, "edit alignments: max_len2 = %d exceeds 3792 (64 windows of packed words in 60 KB of LDS)", max_len2);
-		const int w = max_len1 <= 64 ? 2 : max_len1 <= 96 ? 3 : max_len1 <= 128 ? 4 : max_len1 <= 160 ? 5 : max_len1 <= 256 ? 8 : max_len1 <= 512 ? 16 : 32;
+		const int w = at::class_rows(at::kMyersLaneWords, max_len1);
 		at_edit_tb_fn fn = at_pick_edit_tb(w);
 		if (!fn) return fail(h, AT_ERR_ARG, "no edit alignment kernel for %d words per lane", w);
 		/* the slab: one column is W words x 2 planes x 64 lanes; bounded like the pointer slots of plan_launch */
@@ -1299,8 +1316,7 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		ea.m.order = d_order;
 		ea.ops = d_ops; ea.ops_off = (const long long *)d_ops_off;
 		ea.slab = h->d_ws; ea.slab_words = slab_words;
-		if (!h->d_queue) { HIP_TRY(h, hipMalloc((void **)&h->d_queue, 128)); HIP_TRY(h, hipMemset(h->d_queue, 0, 128)); }
-		HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, 8, stream));
+		if (int rcq = ensure_queue(h, stream)) return rcq;
 		ea.m.queue = h->d_queue;
 		hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, stream, ea);
 		HIP_TRY(h, hipGetLastError());
@@ -1311,7 +1327,7 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 
 	/* ---- edit distance with unit mismatch cost: bit-parallel kernel (at_myers.hip.h), any mix of lengths ---- */
 	/* (bytes of LDS for the s2 windows of the n alignments of a wavefront; two must fit, or the cell-by-cell kernel takes the batch) */
-	auto myers_windows = [&](int n) { return (size_t)n * ((((size_t)max_len2 + 15) / 16 + 2) | 1) * 4; };
+	auto myers_windows = [&](int n) { return at::myers_window_bytes(n, max_len2); };
 	if (kmode == at::K_EDIT && h->u == 1 && bits == 2 && max_len1 <= 32768 && myers_windows(2) <= 60 * 1024 && env_ll("AT_MYERS", 1)) {
 		/* lanes per alignment and words per lane: reads of up to AT_MYERS_LANE_MAX (1 024) bases one alignment per LANE -- 5, 8, 16 or 32
 		 * words, 64 s2 windows in LDS (second sequences of up to ~3 500 bases) -- else 32 lanes; the 16- and 32-word forms only for batches
@@ -1322,8 +1338,7 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		const bool per_lane = max_len1 <= lane_max && max_len1 <= 1024 && myers_windows(64) <= 60 * 1024 &&
 		                      (max_len1 <= 256 || npairs >= env_ll("AT_MYERS_LANE_MIN_PAIRS", 16384)) && env_ll("AT_MYERS_GROUP", 1) == 1;
 		const int g = per_lane ? 1 : max_len1 <= 256 && myers_windows(8) <= 60 * 1024 ? 8 : 32;
-		const int w = per_lane ? (max_len1 <= 64 ? 2 : max_len1 <= 96 ? 3 : max_len1 <= 128 ? 4 : max_len1 <= 160 ? 5 : max_len1 <= 256 ? 8 : max_len1 <= 512 ? 16 : 32)
-		            : max_len1 <= 1024 ? 1 : max_len1 <= 2048 ? 2 : max_len1 <= 4096 ? 4 : max_len1 <= 8192 ? 8 : max_len1 <= 16384 ? 16 : 32;
+		const int w = per_lane ? at::class_rows(at::kMyersLaneWords, max_len1) : at::class_rows(at::kMyersGroupWords, max_len1);
 		at_myers_fn fn = at_pick_myers(w, g);
 		const int per_wave = 64 / g;
 		at::MyersArgs m;
@@ -1334,10 +1349,9 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		m.score = d_score; m.end_i = d_end_i; m.end_j = d_end_j; m.state = d_state; m.nops = d_nops;
 		m.order = d_order;
 		m.ap_n = ap_n; m.ap_first = ap_first;
-		if (!h->d_queue) HIP_TRY(h, hipMalloc((void **)&h->d_queue, 128));
-		HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, 8, stream));
+		if (int rcq = ensure_queue(h, stream)) return rcq;
 		m.queue = h->d_queue;
-		const size_t lds = myers_windows(per_wave);   /* (odd window stride, as the kernel computes it) */
+		const size_t lds = myers_windows(per_wave);
 		if (lds > 60 * 1024) return fail(h, AT_ERR_RANGE, "second sequence too long for the bit-parallel kernel's LDS window");
 		int occ = 0;
 		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, 64, lds) != hipSuccess || occ <= 0) occ = 8;
@@ -1359,10 +1373,9 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 	    npairs < (1LL << 31) - 64 && env_ll("AT_OVERLAP_FILTER", 1)) {
 		/* 2 score <= 2 m b - (2 c - m) D', c = min(m - u, m / 2 - o): needs m >= 0 and 2 c > m */
 		const long long k2 = std::min<long long>(2LL * (h->m - h->u), (long long)h->m - 2LL * h->o) - h->m;
-		auto windows = [&](int n) { return (size_t)n * ((((size_t)max_len2 + 15) / 16 + 2) | 1) * 4; };
-		const int w = max_len1 <= 64 ? 2 : max_len1 <= 96 ? 3 : max_len1 <= 128 ? 4 : max_len1 <= 160 ? 5 : max_len1 <= 256 ? 8 : max_len1 <= 512 ? 16 : 32;
+		const int w = at::class_rows(at::kMyersLaneWords, max_len1);
 		at_myers_fn ffn = at_pick_myers_semi(w);
-		if (h->m >= 0 && k2 > 0 && k2 < 4096 && h->m < 4096 && windows(64) <= 60 * 1024 && ffn) {
+		if (h->m >= 0 && k2 > 0 && k2 < 4096 && h->m < 4096 && myers_windows(64) <= 60 * 1024 && ffn) {
 			int rc = grow(h, &h->d_order, &h->order_bytes, ((size_t)npairs + 64) * 4);
 			if (rc) return rc;
 			int *cand = (int *)h->d_order, *count = cand + ((npairs + 15) & ~15LL);
@@ -1376,10 +1389,9 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			m.ap_n = ap_n; m.ap_first = ap_first;
 			m.semi_m2 = 2 * h->m; m.semi_k = (int)k2; m.semi_min2 = (int)std::max<long long>(std::min<long long>(2LL * h->min_score, INT32_MAX), INT32_MIN);
 			m.cand_order = cand; m.cand_count = count;
-			if (!h->d_queue) { HIP_TRY(h, hipMalloc((void **)&h->d_queue, 128)); HIP_TRY(h, hipMemset(h->d_queue, 0, 128)); }
-			HIP_TRY(h, hipMemsetAsync(h->d_queue, 0, 8, stream));
+			if (int rcq = ensure_queue(h, stream)) return rcq;
 			m.queue = h->d_queue;
-			const size_t lds = windows(64);
+			const size_t lds = myers_windows(64);
 			int occ = 0;
 			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)ffn, 64, lds) != hipSuccess || occ <= 0) occ = 8;
 			const long long fgrid = std::max(1LL, std::min<long long>((npairs + 63) / 64, (long long)occ * h->ncu));
@@ -1690,19 +1702,11 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	uint8_t *d_ops = (uint8_t *)(dout + 5 * b_len1);
 	int64_t *d_poff = (int64_t *)(dout + 5 * b_len1 + b_ops);   /* exclusive prefix sums of nops (tb only) */
 
-	/* ragged batch.  Affine alignments of reads (l1 <= 304, scores within 16 bits) go to the packed kernels in FRAMES
-	 * (RAG kernels): a work item sweeps the extents its alignments need and every alignment keeps its own.
-	 *   local          pairs sorted by (rows-per-lane class of l1, l2), cut into buckets of similar l2, one launch per
-	 *                  bucket on the 16-lane groups; the alignments of an item may differ in l1 and l2
-	 *   global / fit   their end cells lie in row l1, so the alignments of an item share l1: pairs sorted by (l1, l2), every
-	 *                  run of equal l1 padded to whole work items by repeating its last pair (which is then computed twice,
-	 *                  same result to the same place), one launch per rows-per-lane class -- 8-lane groups up to 152 bases,
-	 *                  16-lane groups up to 304; an item sweeps the largest l2 among its own alignments
-	 * Everything else: the int32 kernel, pairs handed out largest first (the work queue is dynamic, so a big pair
-	 * picked up last would otherwise run alone at the end). */
+	/* ragged batch.  Affine alignments of reads whose scores stay within 16 bits (and overlap with tracebacks) go to the packed kernels
+	 * in FRAMES (RAG kernels): a work item sweeps the extents its alignments need and every alignment keeps its own.  The order of the
+	 * pairs and the launches are at_ragplan.h's; everything else runs on the int32 kernel, pairs handed out largest first. */
 	int *d_order = nullptr;
 	bool frames = false;
-	std::vector<int> order;
 	const bool ragged = !uniform && npairs > 1 && npairs < (1LL << 31);
 	if (!ragged) {
 		rc = settle_alphabet();
@@ -1715,73 +1719,29 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 		const bool ovl = mode == AT_MODE_OVERLAP && tb;
 		const int kmode_f = mode == AT_MODE_LOCAL ? at::K_LOCAL : mode == AT_MODE_GLOBAL ? at::K_GLOBAL : mode == AT_MODE_OVERLAP ? at::K_OVERLAP
 		                  : h->use_jump ? at::K_FITJ : at::K_FIT;
-		/* the longest read with a one-strip frame: 32 lanes x 19 rows for local, x 16 for global, x 13 for fit (the uniform kernels'
-		 * classes, layout16_for); overlap: 64 lanes x 16 rows */
-		const int max_rag = mode == AT_MODE_LOCAL ? 608 : mode == AT_MODE_GLOBAL ? 512 : mode == AT_MODE_FIT ? 416 : 1024;
-		/* (group width, rows per lane) of a read length.  Local frames mix read lengths freely and run on the 16-lane groups up to
-		 * 304 bases (on the 8-lane groups, whose lanes carry up to 19 rows, the same batches ran 15 % slower: 100..150 x 100..150 2.9
-		 * against 2.5 ms per 100k pairs), on the 32-lane groups beyond; global / fit: 8-lane groups up to 152 bases, 16-lane up to
-		 * 304, 32-lane beyond; overlap: the 64-lane group with 4 rows per lane up to 256 bases, 16 beyond */
-		auto gclass = [&](int l1) { return ovl ? 64 : l1 > 304 ? 32 : mode == AT_MODE_LOCAL ? 16 : l1 <= 152 ? 8 : 16; };
-		auto kclass = [&](int l1) {
-			if (ovl) return l1 <= 256 ? 4 : 16;
-			if (l1 > 304) return l1 <= 320 ? 10 : l1 <= 384 ? 12 : l1 <= 416 ? 13 : l1 <= 512 ? 16 : 19;
-			if (mode == AT_MODE_LOCAL) return l1 <= 64 ? 4 : l1 <= 80 ? 5 : l1 <= 96 ? 6 : l1 <= 112 ? 7 : l1 <= 160 ? 10 : l1 <= 208 ? 13 : l1 <= 256 ? 16 : 19;
-			return l1 <= 40 ? 5 : l1 <= 48 ? 6 : l1 <= 56 ? 7 : l1 <= 64 ? 8 : l1 <= 80 ? 10 : l1 <= 104 ? 13 : l1 <= 128 ? 16 : l1 <= 152 ? 19 : l1 <= 160 ? 10 : l1 <= 208 ? 13 : l1 <= 256 ? 16 : 19;
-		};
+		/* (a bucket of a local batch is a launch, and the launches of a chunk follow each other on its stream: 4 096 pairs per bucket and
+		 * 33k-pair chunks made up to eight launches per class -- 30..150-base reads 2.24 ms per 100k pairs, 1.92-1.96 with at most two) */
+		const int64_t min_bucket = env_ll("AT_RAGGED_MIN_BUCKET", 16384);
+		at::RagPlan plan;
 		for (int pass = 0; pass < 2; ++pass) {   /* (the second pass: the batch was not pure ACGT after all) */
 			const int planned_bits = bits;
-			order.resize((size_t)npairs);
-			for (int64_t k = 0; k < npairs; ++k) order[(size_t)k] = (int)k;
-			frames = (affine || ovl) && max1 <= max_rag && min1 >= 1 && min2 >= 1 && npairs >= 64 && env_ll("AT_RAGGED_PACKED", 1) &&
+			/* frames: every read within the mode's longest one-strip frame (at_classes.h), scores within 16 bits */
+			frames = (affine || ovl) && max1 <= at::one_strip_top(mode) && min1 >= 1 && min2 >= 1 && npairs >= 64 && env_ll("AT_RAGGED_PACKED", 1) &&
 			         packed_ok(h, mode, bits, max1, max2, ovl ? 2 : 4, &th);
-			/* every frame is at most max1 x max2: if a class has no packed kernel for that (s2 too long for LDS), none is tried */
+			/* every frame is at most max1 x max2: if a group width has no packed kernel for that (s2 too long for LDS), none is tried */
 			if (frames) {
 				const bool hasj = kmode_f == at::K_FITJ;
 				const int tsf = ovl ? 2 : 4;
-				const int tops[4] = {std::min(max1, 152), std::min(max1, 304), std::min(max1, 608), max1};
-				for (int q = 0; q < 4 && frames; ++q) {
-					const int l1q = ovl ? max1 : tops[q];
-					if (l1q < min1 || (q > 0 && !ovl && tops[q] == tops[q - 1])) continue;
-					const int g = gclass(l1q);
-					frames = packed16_kernel_exists(kmode_f, layout16_for(tb, hasj, l1q, max2, tsf, g, ovl, kmode_f, ovl ? kclass(l1q) : 0), tb, tsf, bits, g);
-					if (ovl) break;
+				int prev = -1;
+				for (int gq : at::kRagGroups) {
+					const int l1q = std::min(max1, at::rag_group_top(gq));   /* the longest read of the batch on that width */
+					if (!frames || (ovl && gq != 64) || l1q < min1 || l1q == prev) continue;
+					prev = l1q;
+					const at::GroupRows c = at::rag_class(mode, ovl, l1q);
+					frames = packed16_kernel_exists(kmode_f, layout16_for(tb, hasj, l1q, max2, tsf, c.g, ovl, kmode_f, ovl ? c.k : 0), tb, tsf, bits, c.g);
 				}
 			}
-			if (frames && mode == AT_MODE_LOCAL) {
-				/* (class descending, l2 descending, index ascending): a counting sort -- the key space is 13 x (max2 + 1) */
-				auto kidx = [&](int l1) {   /* classes in descending order of rows */
-					if (l1 > 304) { const int kc = kclass(l1); return kc == 19 ? 0 : kc == 16 ? 1 : kc == 13 ? 2 : kc == 12 ? 3 : 4; }
-					const int kc = kclass(l1);
-					return 5 + (kc == 19 ? 0 : kc == 16 ? 1 : kc == 13 ? 2 : kc == 10 ? 3 : kc == 7 ? 4 : kc == 6 ? 5 : kc == 5 ? 6 : 7);
-				};
-				const size_t span = (size_t)max2 + 1;
-				std::vector<int> start(13 * span + 1, 0);
-				for (int64_t k = 0; k < npairs; ++k) ++start[(size_t)kidx(len1[k]) * span + (size_t)(max2 - len2[k]) + 1];
-				for (size_t q = 1; q < start.size(); ++q) start[q] += start[q - 1];
-				for (int64_t k = 0; k < npairs; ++k) order[(size_t)start[(size_t)kidx(len1[k]) * span + (size_t)(max2 - len2[k])]++] = (int)k;
-			} else if (frames) {
-				/* (l1 descending, l2 descending, index ascending) by counting sort, then every run of equal l1 padded to whole
-				 * work items (16 alignments on the 8-lane groups, 8 on the 16-lane groups, 4 on the 32-lane groups, 2 on the 64-lane group) */
-				const size_t span = (size_t)max2 + 1;
-				std::vector<int> start((size_t)(max1 + 1) * span + 1, 0);
-				for (int64_t k = 0; k < npairs; ++k) ++start[(size_t)(max1 - len1[k]) * span + (size_t)(max2 - len2[k]) + 1];
-				for (size_t q = 1; q < start.size(); ++q) start[q] += start[q - 1];
-				std::vector<int> sorted((size_t)npairs);
-				for (int64_t k = 0; k < npairs; ++k) sorted[(size_t)start[(size_t)(max1 - len1[k]) * span + (size_t)(max2 - len2[k])]++] = (int)k;
-				order.clear();
-				for (size_t b0 = 0; b0 < sorted.size();) {
-					size_t b1 = b0;
-					const size_t run0 = order.size();
-					while (b1 < sorted.size() && len1[sorted[b1]] == len1[sorted[b0]]) order.push_back(sorted[b1++]);
-					const size_t per = (size_t)(2 * (64 / gclass(len1[sorted[b0]])));
-					while ((order.size() - run0) % per) order.push_back(~sorted[b1 - 1]);   /* ~index: swept, not stored (at_sweep16.hip.h) */
-					b0 = b1;
-				}
-			} else
-				std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-					return (int64_t)len1[x] * len2[x] > (int64_t)len1[y] * len2[y];
-				});
+			plan = at::rag_plan(mode, ovl, len1, len2, npairs, max1, max2, min_bucket, frames);
 			if (pass == 0) {
 				rc = settle_alphabet();
 				if (rc) return rc;
@@ -1790,6 +1750,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 		}
 		htrace("chunk: planned, pair", pair_base);
 		/* the order goes up from page-locked memory: nothing to wait for on the host */
+		const std::vector<int> &order = plan.order;
 		rc = grow(h, &h->d_order, &h->order_bytes, order.size() * 4);
 		if (rc) return rc;
 		rc = grow_pinned(h, &h->hp_order, &h->hp_order_bytes, order.size() * 4);
@@ -1797,51 +1758,13 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 		memcpy(h->hp_order, order.data(), order.size() * 4);
 		d_order = (int *)h->d_order;
 		HIP_TRY(h, hipMemcpyAsync(d_order, h->hp_order, order.size() * 4, hipMemcpyHostToDevice, s));
-		if (frames && mode == AT_MODE_LOCAL) {
-			/* (a bucket is a launch, and the launches of a chunk follow each other on its stream: 4 096 pairs per bucket and 33k-pair chunks
-			 * made up to eight launches per class -- 30..150-base reads 2.24 ms per 100k pairs, 1.92-1.96 with at most two) */
-			const int64_t min_bucket = env_ll("AT_RAGGED_MIN_BUCKET", 16384);
-			int nb = 0;
-			for (int64_t b0 = 0; b0 < npairs;) {
-				const int g = gclass(len1[order[(size_t)b0]]), kc = kclass(len1[order[(size_t)b0]]);
-				const int l2first = len2[order[(size_t)b0]];
-				int64_t b1 = b0;
-				int f1 = 0;
-				while (b1 < npairs) {
-					const int x = order[(size_t)b1];
-					if (kclass(len1[x]) != kc || gclass(len1[x]) != g) break;
-					if (b1 - b0 >= min_bucket && (int64_t)len2[x] * 5 < (int64_t)l2first * 4) break;   /* more than 20 % narrower */
-					f1 = std::max(f1, len1[x]);
-					++b1;
-				}
-				rc = align_device(h, mode, b1 - b0, d_words, bits, d_woff1, d_len1, d_woff2, d_len2, f1, l2first, 0, tb ? 1 : 0,
-				                  d_score, d_ei, d_ej, d_st, tb ? d_ops : nullptr, tb ? d_opsoff : nullptr, tb ? d_nops : nullptr, s,
-				                  0, 0, d_order + b0, g);
-				if (rc) return rc;
-				b0 = b1;
-				++nb;
-			}
-			snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " (%d frames)", nb);
-		} else if (frames) {
-			int nb = 0;
-			auto real = [&](size_t q) { return order[q] < 0 ? ~order[q] : order[q]; };   /* (a padding repeat is ~index) */
-			for (size_t b0 = 0; b0 < order.size();) {   /* one launch per (group width, rows per lane) */
-				const int g = gclass(len1[real(b0)]), kc = kclass(len1[real(b0)]);
-				size_t b1 = b0;
-				int f1 = 0, f2 = 0;
-				while (b1 < order.size() && gclass(len1[real(b1)]) == g && kclass(len1[real(b1)]) == kc) {
-					f1 = std::max(f1, len1[real(b1)]); f2 = std::max(f2, len2[real(b1)]);
-					++b1;
-				}
-				rc = align_device(h, mode, (int64_t)(b1 - b0), d_words, bits, d_woff1, d_len1, d_woff2, d_len2, f1, f2, 0, tb ? 1 : 0,
-				                  d_score, d_ei, d_ej, d_st, tb ? d_ops : nullptr, tb ? d_opsoff : nullptr, tb ? d_nops : nullptr, s,
-				                  0, 0, d_order + b0, g);
-				if (rc) return rc;
-				b0 = b1;
-				++nb;
-			}
-			snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " (%d frames, equal-l1 work items)", nb);
+		for (const at::RagLaunch &L : plan.launches) {
+			rc = align_device(h, mode, L.b1 - L.b0, d_words, bits, d_woff1, d_len1, d_woff2, d_len2, L.f1, L.f2, 0, tb ? 1 : 0,
+			                  d_score, d_ei, d_ej, d_st, tb ? d_ops : nullptr, tb ? d_opsoff : nullptr, tb ? d_nops : nullptr, s,
+			                  0, 0, d_order + L.b0, L.g);
+			if (rc) return rc;
 		}
+		if (frames) cfg_append(h, mode == AT_MODE_LOCAL ? " (%d frames)" : " (%d frames, equal-l1 work items)", (int)plan.launches.size());
 	}
 	if (!frames) {
 		rc = align_device(h, mode, npairs, d_words, bits, d_woff1, d_len1, d_woff2, d_len2, max1, max2, uniform ? 1 : 0, tb ? 1 : 0,
@@ -1854,7 +1777,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 		if (host_packed) snprintf(note, sizeof note, " [upload: 2-bit words packed on the host, %d pieces]", up_pieces);
 		else if (caller_pinned) snprintf(note, sizeof note, " [upload: raw bytes from the caller's page-locked memory]");
 		else snprintf(note, sizeof note, " [upload: raw bytes staged, %d pieces]", up_pieces);
-		snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), "%s", note);
+		cfg_append(h, "%s", note);
 	}
 	/* ---- results: the five fixed-size arrays come down in ONE copy into page-locked memory.  Only the bytes of each pair's own
 	 * ---- traceback travel and are written: the used part of every ops slot (or string slot) is packed back to back on the GPU and
@@ -1885,7 +1808,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 		rc = at_cigar_batch_device(h, npairs, d_words, bits, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_opsoff, d_nops, cg->flags,
 		                           (int32_t *)dc, (int32_t *)(dc + al(n * 4)), d_poff, (uint32_t *)(dc + c_head), slots_total, s);
 		if (rc) return rc;
-		snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " [cigar: %d lanes per pair]", h->last_cigar_lanes);
+		cfg_append(h, " [cigar: %d lanes per pair]", h->last_cigar_lanes);
 		/* (the guess is the ops form's, not a measurement of this one: the last batch's payload per pair and a quarter more, and the
 		 * same 64 KiB floor; a handle's first batch assumes four runs per pair) */
 		spec_w = std::min<size_t>((size_t)slots_total, (size_t)(h->last_cigar_per_pair * 1.25 * (double)npairs) + 16384);
@@ -1913,7 +1836,7 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 			rc = at_render_batch_device(h, npairs, d_words, bits, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_opsoff, d_nops,
 			                            d_pk1, d_pk2, d_stroff, 1, s);
 			if (rc) return rc;
-			snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " [strings: %d lanes per pair]", h->last_render_lanes);
+			cfg_append(h, " [strings: %d lanes per pair]", h->last_render_lanes);
 			HIP_TRY(h, hipMemcpyAsync(p_rflag, h->d_rflag, 4, hipMemcpyDeviceToHost, s));
 		}
 		HIP_TRY(h, hipMemcpyAsync(h_poff, d_poff, (size_t)(npairs + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -2084,7 +2007,7 @@ static int align_host_mt(at_handle *h, int mode, int64_t npairs, const uint8_t *
 		}
 	}
 	if (cg) cigar_gather(nchunks, per);
-	snprintf(h->cfg + strlen(h->cfg), sizeof h->cfg - strlen(h->cfg), " x%d chunks", nchunks);
+	cfg_append(h, " x%d chunks", nchunks);
 	return AT_OK;
 }
 

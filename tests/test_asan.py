@@ -82,3 +82,11 @@ def test_c_consumer_host_half_under_sanitizers(asan):
     env = dict(ENV, ASAN_OPTIONS="exitcode=97:detect_leaks=0")   # (the HIP runtime's own start-up allocations are not ours to free)
     rc, out, err = _run([os.path.join(asan, "abi_consumer"), "nogpu"], env=env)
     assert rc == 0 and "host-only ok" in out, out + err
+
+
+def test_row_classes_and_ragged_planner(asan):
+    """The packed kernels' row-class tables (csrc/at_classes.h) against edge lists of the program's own, and the ragged planner
+    (csrc/at_ragplan.h): its invariants over seeded length sets and eight plans pinned by hash -- a stand-alone program
+    (tests/c/ragplan_check.cpp), no GPU and nothing of the library loaded."""
+    rc, out, err = _run([os.path.join(asan, "ragplan_check")])
+    assert rc == 0 and "ragplan_check: ok" in out, out[-3000:] + err[-3000:]
