@@ -26,7 +26,9 @@
  * TS = 4 (scores scaled by 16, |score| < 2048).  TS = 2 trades pointer bits for
  * range: scores scaled by 4 (|score| < 8192, e.g. 1024 x 1024 global), tags
  * L 3 / M 2 / U 1 / J,HOME 0; the pointer nibble then takes bit 0 of the L and U
- * winners' tags (two packed shifts more than TS = 4).
+ * winners' tags (two packed shifts more than TS = 4).  The one-pass local kernels
+ * with TS = 4 have a tag set and a one-instruction pointer cell of their own
+ * (PtrTags below); values, end cells and ops are the same.
  * Local arg-max (alignment.h:830-833, first in row-major order) is tracked
  * once per step: the K cells of the column are reduced with the row index in
  * the (otherwise constant) tag bits, then folded into a per-lane running
@@ -212,6 +214,82 @@ AT_DEV int cell_shift(int sw)
 	 * nibble words on top of each other, steps 0..3 in bits [1:0] of the nibbles, steps 4..7 in bits [3:2] */
 	return PB == 8 ? 8 * sw : PB == 4 ? 8 * (sw & 1) + 4 * (sw >> 1) : 8 * (sw & 1) + 4 * ((sw >> 1) & 1) + 2 * (sw >> 2);
 }
+
+/* The priority tags of the three states and the pointer cell built from them, per kernel family.  Only the order L > M > U > 0
+ * decides the maxima (X: first wins; Ld: extension wins a tie; Uraw: opening wins a tie), so a family may pick the values that
+ * make its cell cheap.
+ *   everything but the one-pass local x16 kernels: L 15 / M 10 / U 1 (x16) or 3 / 2 / 1 (x4) and the cell {bit 3: U winner's tag
+ *     bit, bit 2: L extended, [1:0]: pM}, selected out of the three words with two v_bfi_b32;
+ *   one-pass local, scores x16 (XOR3): L 12 (1100) / M 6 (0110) / U 3 (0011) and the cell m ^ ~(l | u) of the low nibbles of Mraw,
+ *     lraw and Uraw -- one v_bitop3_b32.  m is 12, 6, 3 (the diagonal X winner's tag) or 0 (clamped: HOME), l is 12 (extended) or
+ *     6 (opened), u is 6 (opened) or 3 (extended): u3 = 0, l2 = 1, u1 = 1, l0 = 0, so c3 = m3 ^ ~l3, c2 = m2, c1 = m1, c0 = m0 ^ ~u0 --
+ *     bits [2:1] name m, and with m known bits 3 and 0 give up l and u.  The 4 x 2 x 2 inputs make 16 distinct nibbles.
+ *     Global and fit are left out: their -inf saturates at -32768 and carries no tag at all, so l and u have nibbles beyond those
+ *     two each; a local L or U never saturates (the host's range check).  The two-pass kernels (CK > 0) rebuild their cells in
+ *     replay16_block and walk them in at_walk16.hip.h, both with the first family's tags. */
+template <int MODE, int TS, int CK>
+struct PtrTags {
+	static constexpr bool XOR3 = MODE == K_LOCAL && TS == 4 && CK == 0;
+	static constexpr int L = XOR3 ? 12 : TS == 4 ? 15 : 3, M = XOR3 ? 6 : TS == 4 ? 10 : 2, U = XOR3 ? 3 : 1;
+};
+/* XOR3: the cell of the words Mraw, lraw, Uraw (the low nibble of each 16-bit half counts) ... */
+__host__ __device__ constexpr uint32_t xor3_cell(uint32_t m, uint32_t l, uint32_t u) { return m ^ ~(l | u); }
+/* (in the kernels as the one instruction it is: left to itself hipcc sinks the complement out of every fourth step -- or, xor and a
+ * late xor with -1 instead of one v_bitop3_b32 -- which gives back half of the saving.  The truth table: a = 0xf0, b = 0xcc, c = 0xaa) */
+constexpr uint32_t kXor3Lut = xor3_cell(0xf0u, 0xccu, 0xaau) & 0xffu;
+static_assert(kXor3Lut == 0xe1u, "v_bitop3_b32 computes xor3_cell");
+AT_DEV uint32_t xor3_cell_v(uint32_t m, uint32_t l, uint32_t u)
+{
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+	return __builtin_amdgcn_bitop3_b32(m, l, u, kXor3Lut);
+#else
+	return xor3_cell(m, l, u);
+#endif
+}
+/* ... and the state a walk in state st (3 = L, 2 = M, 1 = U) is in after the cell with the low nibble n: 0 = HOME */
+__host__ __device__ constexpr int xor3_next(int st, uint32_t n)
+{
+	const uint32_t code = (n >> 1) & 3u;                         /* m: 0 -> HOME, 1 -> U, 2 -> L, 3 -> M */
+	const uint32_t m3 = (n >> 2) & ~(n >> 1) & 1u, m0 = ~(n >> 2) & (n >> 1) & 1u;
+	return st == 3 ? (((n >> 3) & 1u) == m3 ? 3 : 2) : st == 2 ? (int)((0xB4u >> (2 * code)) & 3u) : ((n & 1u) == m0 ? 1 : 2);
+}
+/* ... which the walkers read as a table, two bits per nibble value: a shift and a bit-field extract per cell (the formulas above
+ * spelled out cost a walk a dozen instructions per cell -- half of what the sweep saves on C2) */
+__host__ __device__ constexpr uint32_t xor3_table(int st)
+{
+	uint32_t t = 0;
+	for (uint32_t n = 0; n < 16; ++n) t |= (uint32_t)xor3_next(st, n) << (2 * n);
+	return t;
+}
+constexpr bool xor3_proof()
+{
+	for (int st = 1; st <= 3; ++st)
+		for (uint32_t n = 0; n < 16; ++n)
+			if ((int)((xor3_table(st) >> (2 * n)) & 3u) != xor3_next(st, n | 0xabcdef00u)) return false;
+	using T = PtrTags<K_LOCAL, 4, 0>;
+	const uint32_t ms[4] = {(uint32_t)T::L, (uint32_t)T::M, (uint32_t)T::U, 0u}, ls[2] = {(uint32_t)T::L, (uint32_t)T::M}, us[2] = {(uint32_t)T::M, (uint32_t)T::U};
+	const int mstate[4] = {3, 2, 1, 0};
+	const uint32_t junk[4] = {0u, 0xfffffff0u, 0x5a5aa5a0u, 0xa5a55a50u};   /* whatever lies above the nibble */
+	uint32_t seen = 0;
+	for (int m = 0; m < 4; ++m)
+		for (int l = 0; l < 2; ++l)
+			for (int u = 0; u < 2; ++u)
+				for (int j = 0; j < 64; ++j) {
+					const uint32_t c = xor3_cell(ms[m] | junk[j & 3], ls[l] | junk[(j >> 2) & 3], us[u] | junk[j >> 4]);
+					if (xor3_next(2, c) != mstate[m]) return false;               /* in M: the diagonal winner's state */
+					if ((xor3_next(3, c) == 3) != (l == 0)) return false;         /* in L: stays iff L extended */
+					if ((xor3_next(1, c) == 1) != (u == 1)) return false;         /* in U: stays iff U extended */
+					if (xor3_next(3, c) != 3 && xor3_next(3, c) != 2) return false;
+					if (xor3_next(1, c) != 1 && xor3_next(1, c) != 2) return false;
+					if (j == 0) {
+						if (seen & (1u << (c & 15u))) return false;               /* 16 inputs, 16 nibbles */
+						seen |= 1u << (c & 15u);
+					}
+				}
+	return seen == 0xffffu && T::L > T::M && T::M > T::U && T::U > 0 && T::L < 16;
+}
+static_assert(xor3_proof(), "XOR3 cells: the decode returns m's state, `L extended` and `U extended` for all 16 inputs");
+static_assert(PtrTags<K_GLOBAL, 4, 0>::L == 15 && PtrTags<K_LOCAL, 4, 16>::M == 10 && PtrTags<K_LOCAL, 2, 0>::L == 3 && PtrTags<K_FIT, 4, 0>::U == 1, "every other family keeps its tags");
 
 template <bool LDS, int K>
 AT_DEV int pidx(int wr, int r, int lane, int NL)
@@ -682,7 +760,10 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 	/* priority tags in the low bits of every score make v_pk_max pick the reference's first-wins candidate.  They decide
 	 * pointers, never values: the kernels without a pointer matrix (TB = false) run without them, three instructions
 	 * per row-step less, and tag the three end-cell candidates of global only to report the start state. */
-	constexpr int OTGL = TS == 4 ? 15 : 3, OTGM = TS == 4 ? 10 : 2, OTGU = 1;
+	using Tags = PtrTags<MODE, TS, CK>;
+	constexpr bool X3 = Tags::XOR3;           /* one-pass local x16: the tags and the one-instruction cell of their own */
+	constexpr int OTGL = Tags::L, OTGM = Tags::M, OTGU = Tags::U;
+	constexpr uint32_t XT1 = xor3_table(1), XT2 = xor3_table(2), XT3 = xor3_table(3);   /* the walkers' decode of those cells, per state */
 	constexpr int TGL = TB ? OTGL : 0, TGM = TB ? OTGM : 0, TGU = TB ? OTGU : 0;
 	/* Jump state with scores x16: the cell keeps the 4 bits of the other modes and the jump state's own pointer (did J open from
 	 * M here?) goes to a BIT PLANE beside the cells -- one word per 4 rows x 4 steps and half -- 5 bits per cell instead of the 8 of a
@@ -736,7 +817,8 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 	uint32_t c1 = 0x00010001u, umm2 = pk2(a.u16 - a.m16), m2 = pk2(mS);       /* 8-bit alphabets: compare instead of LUT */
 	asm volatile("" : "+v"(c1), "+v"(umm2), "+v"(m2));
 	asm volatile("" : "+v"(o2), "+v"(e2), "+v"(lut_lo), "+v"(lut_hi));
-	asm volatile("" : "+v"(cClean), "+v"(cTagM), "+v"(cTagL), "+v"(cTagU), "+v"(cM3), "+v"(cM7), "+v"(cNib), "+v"(cF0), "+v"(cF000));
+	if constexpr (X3) asm volatile("" : "+v"(cClean), "+v"(cTagM), "+v"(cTagL), "+v"(cTagU), "+v"(cNib), "+v"(cF0), "+v"(cF000));   /* (no cell masks to hold) */
+	else asm volatile("" : "+v"(cClean), "+v"(cTagM), "+v"(cTagL), "+v"(cTagU), "+v"(cM3), "+v"(cM7), "+v"(cNib), "+v"(cF0), "+v"(cF000));
 	const int nstrips = (l1 + RS - 1) / RS;   /* host guarantees 1 when G < 64 */
 	const int tbk_frame = (l2 + G - 1 + BLK - 1) / BLK;
 	const int wps = tbk_frame * RPB * K;      /* pointer word rows per strip (the layout of the slot: always the frame's) */
@@ -1078,7 +1160,7 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 							uint32_t Mraw = padd(diag, S);
 							if constexpr (MODE == K_LOCAL) Mraw = pmax(Mraw, 0u);
 							const uint32_t Mc = TB ? vandor(Mraw, cClean, cTagM) : Mraw;
-							const uint32_t Lc = TB ? (lraw | cTagL) : lraw;
+							const uint32_t Lc = !TB ? lraw : X3 ? vandor(lraw, cClean, cTagL) : (lraw | cTagL);   /* (15 is all ones; 12 is not) */
 							const uint32_t Uraw = pmax(Mo_l[r], padd(U_l[r], e2));
 							const uint32_t Uc = TB ? vandor(Uraw, cClean, cTagU) : Uraw;
 							const uint32_t Mo = padd(Mc, o2);
@@ -1102,7 +1184,10 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 								/* the cell's pointer bits, in the low bits of each 16-bit half (what lies above them is junk
 								 * until the word is assembled): [1:0] pM, bit 2: L extended, bit 3: the U winner's tag bit, bit 4: J opened */
 								uint32_t c;
-								if constexpr (TS == 4) {
+								if constexpr (X3) {
+									/* tags L 12 / M 6 / U 3: one bitwise function of the three words (PtrTags; v_bitop3_b32), decoded by xor3_next */
+									c = xor3_cell_v(Mraw, lraw, Uraw);
+								} else if constexpr (TS == 4) {
 									/* tags L 15 / M 10 / U 1: bit 2 of the L winner (1111 ext / 1010 open), bit 3 of the U winner
 									 * (1010 open / 0001 ext).  (Not their xor: a saturated -inf carries no tag at all.) */
 									c = vbfi(cM7, vbfi(cM3, Mraw, lraw), Uraw);
@@ -1717,9 +1802,9 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 									const uint32_t nb = (w[q] >> sh[q]) & ((1u << PB) - 1u);
 									const int was = st;
 									int op = 0;
-									if (st == 3) { st = (nb & 4u) ? 3 : 2; op = 1; --ci; }
-									else if (st == 2) { st = (int)(nb & 3u); op = 0; --ci; --cj; }
-									else if (st == 1) { st = (TS == 4 ? (nb & 8u) != 0 : (nb & 8u) == 0) ? 2 : 1; op = 2; --cj; }
+									if (st == 3) { st = X3 ? (int)((XT3 >> (2 * nb)) & 3u) : (nb & 4u) ? 3 : 2; op = 1; --ci; }
+									else if (st == 2) { st = X3 ? (int)((XT2 >> (2 * nb)) & 3u) : (int)(nb & 3u); op = 0; --ci; --cj; }
+									else if (st == 1) { st = X3 ? (int)((XT1 >> (2 * nb)) & 3u) : (TS == 4 ? (nb & 8u) != 0 : (nb & 8u) == 0) ? 2 : 1; op = 2; --cj; }
 									else if (HASJ && !JPL) { st = (nb & 16u) ? 2 : 0; op = 3; --cj; }   /* jump state :579-583 (byte cells) */
 									else { ok = false; go = false; }
 									if (ok) {
@@ -1754,7 +1839,8 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 							const bool u_open = TS == 4 ? (nb & 8u) != 0 : (nb & 8u) == 0;
 							const int inL = st == 3, inM = st == 2;
 							const int op = inL ? 1 : inM ? 0 : 2;
-							st = inL ? ((nb & 4u) ? 3 : 2) : inM ? (int)(nb & 3u) : (u_open ? 2 : 1);
+							if constexpr (X3) st = (int)(((inL ? XT3 : inM ? XT2 : XT1) >> (2 * nb)) & 3u);   /* (the cells of the one-pass local x16 kernels: PtrTags) */
+							else st = inL ? ((nb & 4u) ? 3 : 2) : inM ? (int)(nb & 3u) : (u_open ? 2 : 1);
 							ci -= inL | inM; cj -= inL ^ 1;
 							ops[cnt++] = (uint8_t)op;
 						}
