@@ -28,7 +28,7 @@ ERR_ARG, ERR_DOMAIN = -1, -4
 ST_LOW, ST_MID, ST_UPP = 1, 2, 3
 
 # every symbol include/aligntools_hip.h declares
-ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_set_edit_traceback", "at_align_batch",
+ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_set_edit_traceback", "at_set_edit_infix", "at_align_batch",
                "at_align_batch_device", "at_align_allpairs_device", "at_render_batch_device", "at_compact_ops_device",
                "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream", "at_search",
                "at_search_strands", "at_revcomp", "at_revcomp_device",
@@ -98,6 +98,8 @@ def load_library():
     lib.at_set_min_score.argtypes = [C.c_void_p, C.c_int, C.c_int32]
     lib.at_set_edit_traceback.restype = C.c_int
     lib.at_set_edit_traceback.argtypes = [C.c_void_p, C.c_int]
+    lib.at_set_edit_infix.restype = C.c_int
+    lib.at_set_edit_infix.argtypes = [C.c_void_p, C.c_int]
     lib.at_align_batch.restype = C.c_int
     lib.at_align_batch.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -306,6 +308,14 @@ class Aligner:
         second ones of up to 3 792 bases; outside that domain the calls raise.  Off (the default): edit returns the number only."""
         self._check(self._lib.at_set_edit_traceback(self._h, 1 if on else 0))
         self._edit_tb = bool(on)
+
+    def set_edit_infix(self, on=True):
+        """Edit infix mode (at_set_edit_infix): with it on, "edit" is the distance of the best match of s1 INSIDE s2 -- D(0,j) = 0,
+        score = min over j of D(l1,j), end cell (l1, j*) with the smallest such j -- in align_batch, align_batch_strings,
+        align_batch_cigar, cigar and search(..., strands=...); ops (with set_edit_traceback) run from (l1, j*) to (0, j0).  The
+        domain is that of the edit alignments; outside it, and in align_allpairs, the calls raise (never the global number).
+        Off (the default): edit is the global distance."""
+        self._check(self._lib.at_set_edit_infix(self._h, 1 if on else 0))
 
     def align_batch_strings(self, mode, pairs):
         """pairs: list of (s1, s2) bytes/str.  The two gapped strings of every pair, rendered on the GPU

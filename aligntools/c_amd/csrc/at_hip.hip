@@ -14,6 +14,7 @@
 #include "at_revcomp.hip.h"
 #include "at_cigar.hip.h"
 #include "at_edit_tb.hip.h"
+#include "at_infix.hip.h"
 #include "../../../include/aligntools_hip.h"
 
 #include <algorithm>
@@ -97,6 +98,7 @@ struct at_handle {
 	std::vector<int> sites;
 	int min_on = 0, min_score = 0;  /* at_set_min_score: all-vs-all overlap scores skip pairs proven below it */
 	int edit_tb = 0;                /* at_set_edit_traceback: edit batches with want_traceback deliver their ops (at_edit_tb.hip.h) */
+	int edit_infix = 0;             /* at_set_edit_infix: AT_MODE_EDIT is the best match of s1 inside s2 (at_infix.hip.h) */
 	/* device scratch (grow-only) */
 	uint32_t *d_sitemask = nullptr; size_t sitemask_words = 0; int sitemask_for_l2 = -1; bool sitemask_dirty = true;
 	uint32_t *d_ws = nullptr; size_t ws_bytes = 0;
@@ -294,6 +296,13 @@ extern "C" int at_set_edit_traceback(at_handle *h, int enabled)
 {
 	if (!h) return fail(nullptr, AT_ERR_ARG, "at_set_edit_traceback: NULL handle");
 	h->edit_tb = enabled ? 1 : 0;
+	return AT_OK;
+}
+
+extern "C" int at_set_edit_infix(at_handle *h, int enabled)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_set_edit_infix: NULL handle");
+	h->edit_infix = enabled ? 1 : 0;
 	return AT_OK;
 }
 
@@ -1006,6 +1015,65 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 	                : mode == AT_MODE_FIT ? (h->use_jump ? at::K_FITJ : at::K_FIT)
 	                : mode == AT_MODE_OVERLAP ? at::K_OVERLAP : at::K_EDIT;
 
+	/* ---- edit infix mode (at_set_edit_infix): the best match of s1 inside s2 on the bit-parallel path with a zero top border
+	 * (at_infix.hip.h), with the op lists when edit alignments are on and wanted.  Outside the domain the call fails: a global
+	 * distance under an infix setting would be a wrong answer ---- */
+	if (mode == AT_MODE_EDIT && h->edit_infix) {
+		const bool itb = want_traceback && h->edit_tb;
+		const size_t lds = at::myers_window_bytes(64, max_len2);   /* the 64 s2 windows of a wavefront */
+		if (ap_n > 0) return fail(h, AT_ERR_DOMAIN, "edit infix mode: no all-vs-all (pair lists and searches only)");
+		if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "edit infix mode needs the unit mismatch cost: u = %d, not 1", h->u);
+		if (bits != 2) return fail(h, AT_ERR_DOMAIN, "edit infix mode needs a 2-bit batch: some base is not one of ACGT");
+		if (max_len1 > 1024) return fail(h, AT_ERR_DOMAIN, "edit infix mode: max_len1 = %d exceeds 1024", max_len1);
+		if (lds > 60 * 1024) return fail(h, AT_ERR_DOMAIN, "edit infix mode: max_len2 = %d exceeds 3792 (64 windows of packed words in 60 KB of LDS)", max_len2);
+		if (rag || only_if) return fail(h, AT_ERR_ARG, "edit infix mode: not a packed launch");
+		const int w = at::class_rows(at::kMyersLaneWords, max_len1);
+		at_infix_fn fn = at_pick_infix(w, itb ? 1 : 0);
+		if (!fn) return fail(h, AT_ERR_ARG, "no edit infix kernel for %d words per lane", w);
+		int occ = 0;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, 64, lds) != hipSuccess || occ <= 0) occ = 8;
+		at::InfixArgs ia;
+		memset(&ia, 0, sizeof ia);
+		ia.m.npairs = npairs; ia.m.seq = d_seq;
+		ia.m.woff1 = (const long long *)d_woff1; ia.m.woff2 = (const long long *)d_woff2; ia.m.len1 = d_len1; ia.m.len2 = d_len2;
+		ia.m.max_l1 = max_len1; ia.m.max_l2 = max_len2;
+		ia.m.score = d_score; ia.m.end_i = d_end_i; ia.m.end_j = d_end_j; ia.m.state = d_state; ia.m.nops = d_nops;
+		ia.m.order = d_order;
+		if (!itb) {
+			/* sized as the number-only launch of at_myers, one alignment per lane */
+			const long long grid = std::max(1LL, std::min<long long>((npairs + 63) / 64, (long long)occ * h->ncu));
+			if (int rcq = ensure_queue(h, stream)) return rcq;
+			ia.m.queue = h->d_queue;
+			hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, stream, ia);
+			HIP_TRY(h, hipGetLastError());
+			snprintf(h->cfg, sizeof h->cfg, "myers-infix bits=2 words/lane=%d (64 pairs/wave) lds=%zuB waves/cu<=%d grid=%lld", w, lds, occ, grid);
+			return AT_OK;
+		}
+		if (!d_ops || !d_ops_off || !d_nops) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
+		/* the slab of at_edit_tb: one column is W words x 2 planes x 64 lanes; the same caps */
+		const long long slab_words = (long long)std::max(max_len2, 1) * w * 128;
+		const long long cap = env_ll("AT_WS_CAP_MB", 16384) << 20;
+		if (slab_words * 4 > cap)
+			return fail(h, AT_ERR_NOMEM, "edit infix alignments: one work item needs %lld workspace bytes (cap %lld)", slab_words * 4, cap);
+		const long long per_cu = std::max(1LL, std::min<long long>(occ, env_ll("AT_WAVES_PER_CU", 16)));
+		const long long grid = std::max(1LL, std::min<long long>(std::min<long long>((npairs + 63) / 64, per_cu * h->ncu), cap / (slab_words * 4)));
+		{
+			void *p = h->d_ws; size_t have = h->ws_bytes;
+			int rc = grow(h, &p, &have, (size_t)(grid * slab_words * 4), "ws");
+			h->d_ws = (uint32_t *)p; h->ws_bytes = have;
+			if (rc) return rc;
+		}
+		ia.ops = d_ops; ia.ops_off = (const long long *)d_ops_off;
+		ia.slab = h->d_ws; ia.slab_words = slab_words;
+		if (int rcq = ensure_queue(h, stream)) return rcq;
+		ia.m.queue = h->d_queue;
+		hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, stream, ia);
+		HIP_TRY(h, hipGetLastError());
+		snprintf(h->cfg, sizeof h->cfg, "myers-infix-tb bits=2 words/lane=%d (64 pairs/wave) lds=%zuB slab=%lldB waves/cu<=%lld grid=%lld", w, lds,
+		         slab_words * 4, per_cu, grid);
+		return AT_OK;
+	}
+
 	/* ---- packed int16 path: uniform shape, scores provably within 16 bits ---- */
 	/* scores x16 with nibble pointers when they fit (|score| < 2048), else x4 with byte pointers (|score| < 8192) */
 	int thresh16 = 0, ts = 0;
@@ -1523,6 +1591,8 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	if (npairs < 0) return fail(h, AT_ERR_ARG, "negative npairs");
 	if (npairs == 0) return AT_OK;
 	if (!seq_blob || !off1 || !len1 || !off2 || !len2 || !out_score) return fail(h, AT_ERR_ARG, "NULL argument");
+	if (mode == AT_MODE_EDIT && h->edit_infix && h->comm)
+		return fail(h, AT_ERR_DOMAIN, "edit infix mode: one GPU only (this handle belongs to a multi-process job)");
 	const bool tb = want_traceback && (mode != AT_MODE_EDIT || h->edit_tb);
 	const bool strings = out_r1 != nullptr, cigar = cg != nullptr;
 	if (tb && ((!out_ops && !strings && !cigar) || !ops_off || !out_nops)) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
@@ -1973,6 +2043,7 @@ static int align_host_mt(at_handle *h, int mode, int64_t npairs, const uint8_t *
 	for (int c = 0; c < nchunks - 1; ++c) {
 		at_handle *k = h->kids[(size_t)c];
 		k->edit_tb = h->edit_tb;
+		k->edit_infix = h->edit_infix;
 		if (k->m != h->m || k->u != h->u || k->o != h->o || k->e != h->e || k->j != h->j || k->use_jump != h->use_jump ||
 		    k->sites != h->sites) {
 			k->m = h->m; k->u = h->u; k->o = h->o; k->e = h->e; k->j = h->j; k->use_jump = h->use_jump; k->sites = h->sites;
@@ -2100,6 +2171,7 @@ static int check_allpairs_args(at_handle *h, const char *who, int mode, int64_t 
 	if (!h) return fail(nullptr, AT_ERR_ARG, "%s: NULL handle", who);
 	if (mode < AT_MODE_GLOBAL || mode > AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "unknown mode %d", mode);
 	if (mode == AT_MODE_FIT) return fail(h, AT_ERR_ARG, "all-vs-all: fit needs ordered lengths (l1 <= l2); use the pair list entry");
+	if (mode == AT_MODE_EDIT && h->edit_infix) return fail(h, AT_ERR_DOMAIN, "edit infix mode: no all-vs-all (pair lists and searches only)");
 	if (nreads < 2 || nreads >= (1LL << 31) || first_pair < 0 || npairs < 0 || first_pair + npairs > nreads * (nreads - 1) / 2)
 		return fail(h, AT_ERR_ARG, "all-vs-all: pair range [%lld, +%lld) outside the %lld*(%lld-1)/2 ordered pairs",
 		            (long long)first_pair, (long long)npairs, (long long)nreads, (long long)nreads);

@@ -12,6 +12,7 @@
  *   ... --paf (both forms, not edit): one PAF line per pair / hit (at_align_batch_cigar) instead of the name line and two strings.
  *   ... edit -u 1 --alignments (both forms): the alignment behind every distance (at_set_edit_traceback) -- the record the other four
  *       commands print, or with --paf its PAF line.
+ *   ... edit -u 1 --infix (both forms): the distance of the best match of the first sequence inside the second (at_set_edit_infix).
  */
 #define _POSIX_C_SOURCE 200809L
 #include "at_host.h"
@@ -148,6 +149,10 @@ static int main_single(int cmd, int argc, char *argv[])
  *                    the two gapped strings, like the other four commands; with --paf the PAF line -- NM:i is the distance, AS:i
  *                    minus the distance (higher stays better), cg:Z the =/X CIGAR.  Also on the hit pairs of --queries.  Not with
  *                    --score-only, --all-vs-all, --gpus N > 1.
+ *     --infix        (edit -u 1) the distance is that of the best match of the first sequence INSIDE the second (at_set_edit_infix:
+ *                    the read may start and end anywhere in the target); the formats stay, the values are the infix ones -- with
+ *                    --alignments --paf the target start and end columns are where the match lies.  Also on --queries, whose hits
+ *                    then rank by where the read fits.  Not with --all-vs-all, --gpus N > 1.
  *     --gpus N       one process per GPU: this process starts N workers (itself, with AT_RANK / AT_WORLD / AT_DEVICE /
  *                    AT_COMM_DIR in their environment), rank 0's options are broadcast over RCCL, every rank aligns a
  *                    contiguous share of the pairs on its own GPU, results are gathered over RCCL and rank 0 prints them
@@ -156,8 +161,9 @@ static int main_single(int cmd, int argc, char *argv[])
  * thread -- which also pays the HIP start-up, in the shadow of the first chunks' parsing -- sends each chunk to the GPU
  * and writes its results with one fwrite.  Memory is bounded by the chunks in flight, whatever the size of the file;
  * --all-vs-all keeps the read set and streams slices of the triangle instead (at_align_allpairs_stream). */
-typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments; } batch_flags;
+typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments, infix; } batch_flags;
 static int g_edit_alignments;   /* --alignments: every handle of this process delivers edit alignments (set before any handle exists) */
+static int g_edit_infix;        /* --infix: every handle of this process is in edit infix mode (at_set_edit_infix; set likewise) */
 
 /* linear index p of the strict upper triangle of n x n (row-major) -> (a, b), a < b: closed form + integer correction */
 static void tri_seek(int64_t p, int64_t n, int64_t *a, int64_t *b)
@@ -369,6 +375,7 @@ static void *pipe_consumer(void *arg)
 	const opt_t *opt = pp->opt;
 	int rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, opt->s == AT_TRUE, opt->sites.pos, (int)opt->sites.size);
 	if (rc == AT_OK && g_edit_alignments) rc = at_set_edit_traceback(h, 1);
+	if (rc == AT_OK && g_edit_infix) rc = at_set_edit_infix(h, 1);
 	if (rc != AT_OK) die("%s", at_last_error(h));
 	memset(&w, 0, sizeof w);
 	w.paf = pp->paf;
@@ -531,6 +538,7 @@ static int batch_worker(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	h = at_host_handle();
 	rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, opt->s == AT_TRUE, opt->sites.pos, (int)opt->sites.size);
 	if (rc == AT_OK && g_edit_alignments) rc = at_set_edit_traceback(h, 1);
+	if (rc == AT_OK && g_edit_infix) rc = at_set_edit_infix(h, 1);
 	if (rc == AT_OK && comm) {
 		trace("comm: init, rank", rank);
 		rc = at_comm_init(h, rank, world, comm_dir);
@@ -683,6 +691,7 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	h = at_host_handle();
 	rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, opt->s == AT_TRUE, opt->sites.pos, (int)opt->sites.size);
 	if (rc == AT_OK && g_edit_alignments) rc = at_set_edit_traceback(h, 1);
+	if (rc == AT_OK && g_edit_infix) rc = at_set_edit_infix(h, 1);
 	if (rc != AT_OK) die("%s", at_last_error(h));
 	qoff = (int64_t *)at_xmalloc((size_t)nq * 8); qlen = (int32_t *)at_xmalloc((size_t)nq * 4);
 	toff = (int64_t *)at_xmalloc((size_t)nt * 8); tlen = (int32_t *)at_xmalloc((size_t)nt * 4);
@@ -814,10 +823,10 @@ static int main_batch(int argc, char *argv[], char *argv0)
 {
 	int cmd = -1, k, n = 0;
 	opt_t *opt = init_opt();
-	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0};
+	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0, 0};
 	char **av = (char **)at_xmalloc((size_t)(argc + 1) * sizeof(char *));
-	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] [--paf] [--alignments] <pairs.fa>\n"
-	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] <targets.fa>\n";
+	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] [--paf] [--alignments] [--infix] <pairs.fa>\n"
+	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] [--infix] <targets.fa>\n";
 	/* the long flags of the extension are taken out before getopt sees the reference's short options */
 	for (k = 0; k < argc; ++k) {
 		if (strcmp(argv[k], "--score-only") == 0) bf.score_only = 1;
@@ -829,6 +838,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (strcmp(argv[k], "--both-strands") == 0) bf.both = 1;
 		else if (strcmp(argv[k], "--paf") == 0) bf.paf = 1;
 		else if (strcmp(argv[k], "--alignments") == 0) bf.alignments = 1;
+		else if (strcmp(argv[k], "--infix") == 0) bf.infix = 1;
 		else av[n++] = argv[k];
 	}
 	av[n] = NULL;
@@ -848,6 +858,9 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (bf.alignments && bf.score_only) why = "--alignments does not go with --score-only";
 		else if (bf.alignments && bf.all_vs_all) why = "--alignments does not go with --all-vs-all";
 		else if (bf.alignments && bf.gpus > 1) why = "--alignments runs on one GPU: it does not go with --gpus N > 1";
+		else if (bf.infix && cmd != C_EDIT) why = "--infix goes with edit";
+		else if (bf.infix && bf.all_vs_all) why = "--infix does not go with --all-vs-all";
+		else if (bf.infix && bf.gpus > 1) why = "--infix runs on one GPU: it does not go with --gpus N > 1";
 		else if (bf.paf && cmd == C_EDIT && !bf.alignments) why = "--paf does not go with edit (edit has no alignment)";
 		else if (bf.paf && bf.score_only) why = "--paf does not go with --score-only (a PAF line needs the traceback)";
 		else if (bf.paf && bf.all_vs_all) why = "--paf does not go with --all-vs-all";
@@ -860,7 +873,9 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	if (parse_opts(cmd, n - 1, av + 1, opt)) { free(opt); free(av); return 1; }
 	if (optind + 1 > n - 1) { cmd_usage(cmd, opt); free(opt); free(av); return 1; }
 	if (bf.alignments && opt->u != 1) { fprintf(stderr, "--alignments needs -u 1\n%s", usage_line); free(opt); free(av); return 1; }
+	if (bf.infix && opt->u != 1) { fprintf(stderr, "--infix needs -u 1\n%s", usage_line); free(opt); free(av); return 1; }
 	g_edit_alignments = bf.alignments;
+	g_edit_infix = bf.infix;
 	if (bf.queries) {
 		k = batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
 		free(opt->sites.pos); free(opt); free(av);

@@ -195,6 +195,35 @@ int at_set_min_score(at_handle *h, int enabled, int32_t min_score);
 int at_set_edit_traceback(at_handle *h, int enabled);
 
 /*
+ * Edit INFIX mode: the best match of s1 (a read) inside s2 (a target) -- approximate matching in Myers' sense: the read may start
+ * anywhere in the target and end anywhere.  A per-handle setting; enabled = 0 (the default) changes nothing anywhere.  With it on,
+ * AT_MODE_EDIT means (the rule is this library's; the reference's edit_dist, alignment.h:291-315, is global only):
+ *   table   D(0,j) = 0, D(i,0) = i, D(i,j) = min(D(i,j-1) + 1, D(i-1,j-1) + (s1[i-1] != s2[j-1]), D(i-1,j) + 1)
+ *   result  score = min over 0 <= j <= l2 of D(l1,j); end cell (l1, j*) with j* the SMALLEST j that attains the minimum (first wins,
+ *           like the local arg-max); state AT_ST_MID.  l1 = 0: score 0, j* = 0.  l2 = 0: score l1, j* = 0.  l1 > l2 is allowed (the
+ *           score is then at least l1 - l2)
+ *   ops     delivered when at_set_edit_traceback is on as well and want_traceback is set; END -> START from (l1, j*) until i == 0,
+ *           at cell (i, j) the first rule that holds:
+ *             1. j > 0 && D(i-1,j-1) + (s1[i-1] != s2[j-1]) == D(i,j)    AT_OP_MID, i--, j--
+ *             2. D(i-1,j) + 1 == D(i,j)                                  AT_OP_LOW, i--
+ *             3. otherwise                                               AT_OP_UPP, j--
+ *           (at j == 0 rule 2 always holds.)  The walk ends in (0, j0); nops <= l1 + l2; mismatch columns plus gap columns equal the
+ *           score.  j0 is the target start: AT_CG_START_J of the statistics row and the target start column of a PAF line, both
+ *           derived as ever from the end cell minus the columns consumed.
+ * Examples: ACGT in ACGTACGTACGT: score 0, j* = 4, four MID.  ACGTA in CG: score 3, j* = 2, ops LOW LOW MID MID LOW.
+ * at_align_batch, at_align_batch_device, at_align_batch_strings, at_align_batch_cigar, at_search and at_search_strands follow the
+ * setting (a search then ranks targets by where the read fits, every (query, target) pair a candidate whatever the lengths; a hit's
+ * score, end cell and state are exactly what at_align_batch returns for that pair).
+ * The domain is that of the edit alignments: mismatch cost u == 1, a 2-bit (pure ACGT) batch, max_len1 <= 1 024, max_len2 <= 3 792 (64
+ * windows of packed words in 60 KB of LDS).  Outside it the call fails with AT_ERR_DOMAIN and a text that names the broken bound; it
+ * never falls back to the global number, which under this setting would be a wrong answer.  For the same reason the all-pairs
+ * entries in edit mode fail with AT_ERR_DOMAIN while the setting is on, and so does an edit batch on a handle that has joined a
+ * multi-process job (at_comm_init: the setting is not broadcast to the other ranks).  The reference-named single-pair surface of aligntools.h never turns it on.
+ * Kernels: csrc/at_infix.hip.h; at_last_config begins "myers-infix" (number only) or "myers-infix-tb" (with ops).
+ */
+int at_set_edit_infix(at_handle *h, int enabled);
+
+/*
  * The same sweep with bounded memory, for triangles too large to hold (C5: 50 000 reads = 1.25e9 pairs = 20 GB of
  * results): scores and end cells only, the triangle cut into slices of at most chunk_pairs pairs (<= 0: 4 Mi); `fn`
  * is called once per slice, in pair order, on the calling thread, while the GPU already sweeps the next slice.  The
