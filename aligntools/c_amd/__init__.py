@@ -31,7 +31,7 @@ ST_LOW, ST_MID, ST_UPP = 1, 2, 3
 ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_set_edit_traceback", "at_set_edit_infix", "at_align_batch",
                "at_align_batch_device", "at_align_allpairs_device", "at_render_batch_device", "at_compact_ops_device",
                "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream", "at_search",
-               "at_search_strands", "at_revcomp", "at_revcomp_device",
+               "at_search_strands", "at_scan", "at_scan_plan", "at_revcomp", "at_revcomp_device",
                "at_cigar", "at_cigar_batch_device", "at_align_batch_cigar",
                "at_comm_init", "at_comm_broadcast_scoring", "at_comm_allgather", "at_comm_destroy", "at_comm_abi_checked",
                "at_pack_words", "at_pack_batch", "at_render", "at_last_config"]
@@ -132,6 +132,11 @@ def load_library():
     lib.at_search_strands.restype = C.c_int
     lib.at_search_strands.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int] + [C.c_void_p] * 7
+    lib.at_scan.restype = C.c_int
+    lib.at_scan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_int, C.c_int, C.c_int32, C.c_int, C.c_int32, C.c_int] + [C.c_void_p] * 11 + [C.c_int64]
+    lib.at_scan_plan.restype = C.c_int
+    lib.at_scan_plan.argtypes = [C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int32, _i32p, _i32p, _i64p]
     lib.at_revcomp.restype = C.c_int
     lib.at_revcomp.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.at_revcomp_device.restype = C.c_int
@@ -218,6 +223,18 @@ def revcomp(s):
     if rc:
         raise AlignToolsError(rc, lib.at_last_error(None).decode())
     return out.raw[:len(s)]
+
+
+def scan_plan(len1, len2, cutoff=None, tile_cols=0):
+    """Host helper (at_scan_plan): how Aligner.scan cuts a pair of len1 x len2 -- (tile, overlap, ngroups): the columns a lane owns,
+    the warm-up columns in front of a tile and the groups of 64 tiles."""
+    lib = load_library()
+    tile, ov, ng = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    rc = lib.at_scan_plan(int(len1), int(len2), 0 if cutoff is None else 1, 0 if cutoff is None else int(cutoff), int(tile_cols),
+                          C.byref(tile), C.byref(ov), C.byref(ng))
+    if rc:
+        raise AlignToolsError(rc, lib.at_last_error(None).decode())
+    return tile.value, ov.value, ng.value
 
 
 def cigar(ops, s1, end_i, s2, end_j, extended=True):
@@ -501,6 +518,56 @@ class Aligner:
                                         _ptr(out["target"]), _ptr(out["score"]), _ptr(out["end_i"]), _ptr(out["end_j"]),
                                         _ptr(out["state"]), _ptr(nhits)))
         out["nhits"] = nhits
+        return out
+
+    def scan(self, queries, targets, k=1, cutoff=None, strands="forward", cigar=False, cigar_m=False, tile_cols=0):
+        """Reads against long targets (at_scan): for every query the best `k` hits over the targets, a hit being the best match of
+        the query inside a target under the rule of set_edit_infix -- whatever that setting says -- with no bound on the target
+        length.  Queries of up to 1 024 bases, ACGT, u == 1.  Returns the dict of search("edit", ...) (end_j is the absolute
+        column; `strand` with "reverse" / "both") and, with cigar=True, per hit entry stats (nq, k, 8), ncigar (nq, k) and cigar, a
+        list of nq lists of k numpy uint32 arrays ('=' / 'X'; cigar_m: 'M'); an unused entry has no runs and a row of -1.
+        tile_cols: the columns a lane owns (a multiple of 16; 0: the default) -- the results do not depend on it."""
+        if strands not in STRANDS:
+            raise ValueError("strands must be one of %s" % ", ".join(sorted(STRANDS)))
+        qs = [_b(x) for x in queries]
+        ts = [_b(x) for x in targets]
+        nq, nt, k = len(qs), len(ts), int(k)
+
+        def pack(seqs):
+            lens = np.fromiter((len(x) for x in seqs), dtype=np.int32, count=len(seqs))
+            off = np.zeros(len(seqs), dtype=np.int64)
+            if len(seqs) > 1:
+                np.cumsum(lens[:-1], out=off[1:])
+            return np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8).copy(), off, lens
+        qb, qo, ql = pack(qs)
+        tb, to, tl = pack(ts)
+        kk = max(k, 0)
+        out = {name: np.full((nq, kk), -1 if name == "target" else 0, dtype=np.int32)
+               for name in ("target", "score", "end_i", "end_j", "state")}
+        nhits = np.zeros(nq, dtype=np.int32)
+        strand = np.full((nq, kk), -1, dtype=np.int32)
+        n = nq * kk
+        stats = np.full((nq, kk, 8), -1, dtype=np.int32) if cigar else None
+        ncigar = np.zeros((nq, kk), dtype=np.int32) if cigar else None
+        cigar_off = np.zeros(n + 1, dtype=np.int64) if cigar else None
+        cap = 16 * n + 64                                      # a second call if the hits have more runs than that
+        for _ in range(2):
+            words = np.zeros(cap, dtype=np.uint32) if cigar else None
+            self._check(self._lib.at_scan(self._h, nq, _ptr(qb), _ptr(qo), _ptr(ql), nt, _ptr(tb), _ptr(to), _ptr(tl), k,
+                                          0 if cutoff is None else 1, 0 if cutoff is None else int(cutoff), STRANDS[strands],
+                                          int(tile_cols), CIGAR_M if cigar_m else 0, _ptr(out["target"]), _ptr(out["score"]),
+                                          _ptr(out["end_i"]), _ptr(out["end_j"]), _ptr(out["state"]), _ptr(strand), _ptr(nhits),
+                                          _ptr(stats), _ptr(ncigar), _ptr(cigar_off), _ptr(words), cap if cigar else 0))
+            if not cigar or cigar_off[n] <= cap:
+                break
+            cap = int(cigar_off[n])
+        if strands != "forward":
+            out["strand"] = strand
+        out["nhits"] = nhits
+        if cigar:
+            out["stats"], out["ncigar"], out["cigar_off"] = stats, ncigar, cigar_off
+            out["cigar"] = [[words[cigar_off[q * kk + e]:cigar_off[q * kk + e] + max(int(ncigar[q, e]), 0)].copy() for e in range(kk)]
+                            for q in range(nq)]
         return out
 
     def align_allpairs_device(self, mode, nreads, d_seq, bits, d_woff, d_len, max_len, first_pair, npairs, want_traceback,

@@ -15,6 +15,7 @@
 #include "at_cigar.hip.h"
 #include "at_edit_tb.hip.h"
 #include "at_infix.hip.h"
+#include "at_scan.hip.h"
 #include "../../../include/aligntools_hip.h"
 
 #include <algorithm>
@@ -2445,6 +2446,314 @@ extern "C" int at_search(at_handle *h, int mode,
 {
 	return at_search_strands(h, mode, nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len, k, use_cutoff, cutoff, AT_STRAND_FWD,
 	                         out_target, out_score, out_end_i, out_end_j, out_state, nullptr, out_nhits);
+}
+
+/* ---- reads against long targets (at_scan; at_scan.hip.h) ---- */
+extern "C" int at_scan_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutoff, int32_t tile_cols,
+                            int32_t *tile, int32_t *overlap, int64_t *ngroups)
+{
+	at::ScanPlan sp;
+	if (len1 < 0 || len2 < 0) return fail(nullptr, AT_ERR_ARG, "at_scan_plan: negative length");
+	if (at::scan_plan(len1, len2, use_cutoff, cutoff, tile_cols, &sp) != AT_OK)
+		return fail(nullptr, AT_ERR_ARG, "at_scan_plan: tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)", tile_cols,
+		            at::kScanDefaultTile);
+	if (tile) *tile = sp.tile;
+	if (overlap) *overlap = sp.overlap;
+	if (ngroups) *ngroups = sp.ngroups;
+	return AT_OK;
+}
+
+static const char *scan_strands_text(int strands) { return strands == AT_STRAND_REV ? "rev" : strands == AT_STRAND_BOTH ? "both" : "fwd"; }
+
+/* the lists of at_scan: the blocks and slices of search_lists with the targets in caller order; per slice the key slots are set,
+ * the groups of its pairs swept, the keys unpacked and merged (at_scan.hip.h).  The lists stay in h->d_str behind the call. */
+static int scan_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64_t nt, const int32_t *t_len, const ReadSet &rs,
+                      int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile, int32_t *out_target, int32_t *out_score,
+                      int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state, int32_t *out_strand, int32_t *out_nhits,
+                      size_t *list_bkey, size_t *list_b4)
+{
+	const int enc = strands != AT_STRAND_FWD, two = strands == AT_STRAND_BOTH;
+	const int64_t nv = nq << two;
+	std::vector<int> qs((size_t)nq), qperm((size_t)nv), tperm((size_t)nt);
+	for (int64_t q = 0; q < nq; ++q) qs[(size_t)q] = (int)q;
+	for (int64_t t = 0; t < nt; ++t) tperm[(size_t)t] = (int)t;
+	std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
+	for (int64_t q = 0; q < nq; ++q) {
+		const int c = qs[(size_t)q];
+		if (two) { qperm[(size_t)(2 * q)] = c << 1; qperm[(size_t)(2 * q + 1)] = (c << 1) | 1; }
+		else qperm[(size_t)q] = enc ? (c << 1) | 1 : c;
+	}
+	std::vector<long long> gpre((size_t)nt + 1);
+	gpre[0] = 0;
+	for (int64_t t = 0; t < nt; ++t) gpre[(size_t)t + 1] = gpre[(size_t)t] + at::scan_groups(t_len[t], tile);
+	const long long gall = gpre[(size_t)nt];
+	struct Block { int qa, nqb; int32_t l1; };
+	std::vector<Block> blocks;
+	int64_t most = 0;
+	for (int64_t a = 0, b; a < nq; a = b) {
+		const int32_t L = q_len[qs[(size_t)a]];
+		for (b = a; b < nq && q_len[qs[(size_t)b]] == L; ++b) {}
+		blocks.push_back({(int)(a << two), (int)((b - a) << two), L});
+		most = std::max<int64_t>(most, ((b - a) << two) * nt);
+	}
+	int64_t chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
+	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(std::max<int64_t>(most, 1), 1LL << 28)));
+	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	const size_t b8 = al((size_t)chunk * 8), b4 = al((size_t)chunk * 4), bq = al((size_t)nv * 4), bt = al((size_t)nt * 4), bg = al(((size_t)nt + 1) * 8);
+	const size_t nl = (size_t)nq * (size_t)k, bkey = al(nl * 8), bl4 = al(nl * 4);
+	int rc = grow(h, &h->d_desc, &h->desc_bytes, b8 + bg + bq + bt);
+	if (rc) return rc;
+	rc = grow(h, &h->d_out, &h->out_bytes, 4 * b4);
+	if (rc) return rc;
+	const size_t lbytes = bkey + 3 * bl4 + 256;
+	rc = grow(h, &h->d_str, &h->str_bytes, lbytes);
+	if (rc) return rc;
+	char *dd = (char *)h->d_desc, *dr = (char *)h->d_out, *dl = (char *)h->d_str;
+	unsigned long long *d_pkey = (unsigned long long *)dd;
+	long long *d_gpre = (long long *)(dd + b8);
+	int *d_qperm = (int *)(dd + b8 + bg), *d_tperm = (int *)(dd + b8 + bg + bq);
+	int32_t *d_sc = (int32_t *)dr, *d_ei = (int32_t *)(dr + b4), *d_ej = (int32_t *)(dr + 2 * b4), *d_st = (int32_t *)(dr + 3 * b4);
+	unsigned long long *d_key = (unsigned long long *)dl;
+	int *d_lei = (int *)(dl + bkey), *d_lej = (int *)(dl + bkey + bl4), *d_lst = (int *)(dl + bkey + 2 * bl4), *d_bad = (int *)(dl + bkey + 3 * bl4);
+	hipStream_t s = h->stream;
+	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nv * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_tperm, tperm.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_gpre, gpre.data(), ((size_t)nt + 1) * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemsetAsync(dl, 0, lbytes, s));
+	std::string cfg0;
+	int64_t nslices = 0;
+	int ov_most = 0;
+	/* the device time of the sweep phase (key slots, groups, unpack, merge of every slice) goes into at_last_config: tools/edit_scan_rate.py */
+	struct Ev { hipEvent_t e[2] = {nullptr, nullptr}; ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
+	for (hipEvent_t &x : ev.e) HIP_TRY(h, hipEventCreate(&x));
+	HIP_TRY(h, hipEventRecord(ev.e[0], s));
+	auto items_before = [&](int64_t x) { return (long long)(x / nt) * gall + gpre[(size_t)(x % nt)]; };   /* items of the block's pairs [0, x) */
+	for (const Block &B : blocks) {
+		const int64_t bp = (int64_t)B.nqb * nt;
+		const int w = at::class_rows(at::kMyersLaneWords, B.l1);
+		const void *fn = at_scan_kernel(w);
+		if (!fn) return fail(h, AT_ERR_ARG, "no scan kernel for %d words per lane", w);
+		int occ = 0;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64, 0) != hipSuccess || occ <= 0) occ = 8;
+		ov_most = std::max(ov_most, (int)at::scan_overlap(B.l1, use_cutoff, cutoff));
+		for (int64_t s0 = 0; s0 < bp; s0 += chunk) {
+			const int64_t n = std::min(chunk, bp - s0);
+			at::ScanArgs sa;
+			memset(&sa, 0, sizeof sa);
+			sa.y0 = items_before(s0); sa.nitems = items_before(s0 + n) - sa.y0;
+			sa.s0 = s0; sa.npairs = n; sa.ntb = nt; sa.gall = gall; sa.gpre = d_gpre;
+			sa.qa = B.qa; sa.nq = (int)nq; sa.enc = enc; sa.nrev0 = (int)(nq + nt); sa.qperm = d_qperm;
+			sa.seq = rs.d_words; sa.swoff = (const long long *)rs.d_swoff; sa.slen = rs.d_len;
+			sa.tile = tile; sa.use_cutoff = use_cutoff ? 1 : 0; sa.cutoff = cutoff;
+			sa.key = d_pkey; sa.score = d_sc; sa.end_i = d_ei; sa.end_j = d_ej; sa.state = d_st;
+			HIP_TRY(h, at_scan_init_launch(&sa, h->ncu, s));
+			if (int rcq = ensure_queue(h, s)) return rcq;
+			sa.queue = h->d_queue;
+			const long long grid = std::max(1LL, std::min<long long>(sa.nitems, (long long)occ * h->ncu));
+			HIP_TRY(h, at_scan_launch(&sa, w, (unsigned)grid, s));
+			HIP_TRY(h, at_scan_unpack_launch(&sa, h->ncu, s));
+			if (nslices == 0) {
+				char buf[200];
+				snprintf(buf, sizeof buf, "myers-scan bits=2 words/lane=%d (1 read/wave, 64 tiles) lds=0B waves/cu<=%d grid=%lld", w, occ, grid);
+				cfg0 = buf;
+			}
+			at::SearchMergeArgs ma;
+			memset(&ma, 0, sizeof ma);
+			ma.s0 = s0; ma.n = n; ma.ntb = nt; ma.qa = B.qa; ma.ta = 0;
+			ma.enc = enc; ma.two = two;
+			ma.nqs = (int)((s0 + n - 1) / (nt << two) - s0 / (nt << two) + 1);
+			ma.qperm = d_qperm; ma.tperm = d_tperm;
+			ma.score = d_sc; ma.end_i = d_ei; ma.end_j = d_ej; ma.state = d_st;
+			ma.k = k; ma.is_edit = 1; ma.use_cutoff = use_cutoff ? 1 : 0; ma.cutoff = cutoff;
+			ma.lkey = d_key; ma.lei = d_lei; ma.lej = d_lej; ma.lst = d_lst; ma.bad = d_bad;
+			HIP_TRY(h, at_search_merge_launch(&ma, s));
+			++nslices;
+		}
+	}
+	HIP_TRY(h, hipEventRecord(ev.e[1], s));
+	std::vector<char> hl(lbytes);
+	HIP_TRY(h, hipMemcpyAsync(hl.data(), dl, lbytes, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipStreamSynchronize(s));
+	float sweep_ms = 0.f;
+	HIP_TRY(h, hipEventElapsedTime(&sweep_ms, ev.e[0], ev.e[1]));
+	const unsigned long long *hk = (const unsigned long long *)hl.data();
+	const int32_t *hei = (const int32_t *)(hl.data() + bkey), *hej = (const int32_t *)(hl.data() + bkey + bl4), *hst = (const int32_t *)(hl.data() + bkey + 2 * bl4);
+	for (int64_t q = 0; q < nq; ++q) {
+		int nh = 0;
+		for (int j = 0; j < k; ++j) {
+			const size_t e = (size_t)q * k + j;
+			if (!hk[e]) break;
+			const int32_t r = (int32_t)((uint32_t)(hk[e] >> 32) ^ 0x80000000u);
+			const uint32_t low = ~(uint32_t)hk[e];
+			out_target[e] = (int32_t)(low >> enc);
+			if (out_strand) out_strand[e] = enc ? (int32_t)(low & 1u) : 0;
+			out_score[e] = -r;
+			out_end_i[e] = hei[e]; out_end_j[e] = hej[e]; out_state[e] = hst[e];
+			++nh;
+		}
+		out_nhits[q] = nh;
+	}
+	snprintf(h->cfg, sizeof h->cfg, "scan: tile=%d overlap<=%d groups=%lld k=%d strands=%s, %lld blocks, %lld slices; %s sweep=%.3fms", tile, ov_most, gall, k,
+	         scan_strands_text(strands), (long long)blocks.size(), (long long)nslices, cfg0.c_str(), (double)sweep_ms);
+	*list_bkey = bkey; *list_b4 = bl4;
+	return AT_OK;
+}
+
+/* the alignments of the hits: every list entry as a window pair through at_infix<W, true> and the CIGAR kernels (at_scan.hip.h) */
+static int scan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadSet &rs, int64_t nt, int32_t maxq, size_t bkey, size_t bl4,
+                       const int32_t *out_target, const int32_t *out_score, const int32_t *out_end_i, const int32_t *out_end_j, int flags,
+                       int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap)
+{
+	const int enc = strands != AT_STRAND_FWD;
+	const int64_t n = nq * k;
+	/* ops slots: l1 + window columns per hit, back to back */
+	std::vector<int64_t> slot((size_t)n);
+	int64_t ops_bytes = 0;
+	int32_t max2 = 0;
+	for (int64_t e = 0; e < n; ++e) {
+		slot[(size_t)e] = ops_bytes;
+		if (out_target[e] < 0) continue;
+		const int32_t len2 = (int32_t)(out_end_j[e] - at::scan_window_start(out_end_j[e], out_end_i[e], out_score[e]));
+		ops_bytes += (int64_t)out_end_i[e] + len2;
+		max2 = std::max(max2, len2);
+	}
+	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	const size_t b8 = al((size_t)(n + 1) * 8), b4 = al((size_t)n * 4), bst = al((size_t)n * 32);
+	const int64_t dcap = std::min<int64_t>(cigar_cap, ops_bytes);   /* (a list has no more runs than ops) */
+	int rc = grow(h, &h->d_out, &h->out_bytes, 3 * b8 + 8 * b4);
+	if (rc) return rc;
+	rc = grow(h, &h->d_order, &h->order_bytes, (size_t)ops_bytes + 256);
+	if (rc) return rc;
+	rc = grow(h, &h->d_cg, &h->cg_bytes, 2 * b4 + bst + b8 + al((size_t)dcap * 4) + 256);
+	if (rc) return rc;
+	char *dw = (char *)h->d_out, *dc = (char *)h->d_cg, *dl = (char *)h->d_str;
+	int64_t *d_woff1 = (int64_t *)dw, *d_woff2 = (int64_t *)(dw + b8), *d_ops_off = (int64_t *)(dw + 2 * b8);
+	int32_t *d4[8];
+	for (int x = 0; x < 8; ++x) d4[x] = (int32_t *)(dw + 3 * b8 + (size_t)x * b4);
+	int32_t *d_len1 = d4[0], *d_len2 = d4[1], *d_ws = d4[2], *d_sc = d4[3], *d_ei = d4[4], *d_ej = d4[5], *d_st = d4[6], *d_nops = d4[7];
+	int32_t *d_ncigar = (int32_t *)dc, *d_ncout = (int32_t *)(dc + b4), *d_stats = (int32_t *)(dc + 2 * b4);
+	int64_t *d_coff = (int64_t *)(dc + 2 * b4 + bst);
+	uint32_t *d_cigar = (uint32_t *)(dc + 2 * b4 + bst + b8);
+	int *d_bad = (int *)(dc + 2 * b4 + bst + b8 + al((size_t)dcap * 4));
+	uint8_t *d_ops = (uint8_t *)h->d_order;
+	hipStream_t s = h->stream;
+	HIP_TRY(h, hipMemcpyAsync(d_ops_off, slot.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemsetAsync(d_bad, 0, 4, s));
+	at::ScanWindowArgs wa;
+	memset(&wa, 0, sizeof wa);
+	wa.n = n; wa.k = k; wa.nq = (int)nq; wa.enc = enc; wa.nrev0 = (int)(nq + nt);
+	wa.lkey = (const unsigned long long *)dl; wa.lej = (const int *)(dl + bkey + bl4);
+	wa.swoff = (const long long *)rs.d_swoff; wa.slen = rs.d_len;
+	wa.woff1 = (long long *)d_woff1; wa.woff2 = (long long *)d_woff2; wa.len1 = d_len1; wa.len2 = d_len2; wa.ws = d_ws;
+	wa.w_score = d_sc; wa.w_end_j = d_ej; wa.ncigar = d_ncigar; wa.stats = d_stats; wa.ncigar_out = d_ncout; wa.bad = d_bad;
+	HIP_TRY(h, at_scan_window_launch(&wa, h->ncu, s));
+	const std::string cfg0 = h->cfg;
+	{
+		/* the window pass is an infix batch with op lists whatever the handle's settings say; they are put back at once */
+		const int keep_infix = h->edit_infix, keep_tb = h->edit_tb;
+		h->edit_infix = 1; h->edit_tb = 1;
+		rc = align_device(h, AT_MODE_EDIT, n, rs.d_words, 2, d_woff1, d_len1, d_woff2, d_len2, maxq, max2, 0, 1, d_sc, d_ei, d_ej, d_st,
+		                  d_ops, d_ops_off, d_nops, s, 0, 0);
+		h->edit_infix = keep_infix; h->edit_tb = keep_tb;
+	}
+	if (rc) { (void)hipStreamSynchronize(s); return rc; }
+	const std::string cfg1 = h->cfg;
+	rc = at_cigar_batch_device(h, n, rs.d_words, 2, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_ops_off, d_nops, flags, d_ncigar, d_stats, d_coff,
+	                           d_cigar, dcap, s);
+	if (rc) { (void)hipStreamSynchronize(s); return rc; }
+	HIP_TRY(h, at_scan_check_launch(&wa, h->ncu, s));
+	int bad = 0;
+	HIP_TRY(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipMemcpyAsync(out_ncigar, d_ncout, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipMemcpyAsync(out_stats, d_stats, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipMemcpyAsync(out_cigar_off, d_coff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipStreamSynchronize(s));
+	if (bad) return fail(h, AT_ERR_RANGE, "at_scan: a hit's window does not reproduce its score and end column (target columns [ws, j*) of at most %d)", max2);
+	/* the words of the entries that end within the caller's capacity: a prefix of the device buffer */
+	int64_t fit = 0;
+	for (int64_t e = 0; e < n; ++e) if (out_cigar_off[e + 1] <= cigar_cap) fit = out_cigar_off[e + 1]; else break;
+	if (fit > 0) {
+		HIP_TRY(h, hipMemcpyAsync(out_cigar, d_cigar, (size_t)fit * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(h, hipStreamSynchronize(s));
+	}
+	snprintf(h->cfg, sizeof h->cfg, "%.300s; windows: %.200s, cigars: %d lanes/pair", cfg0.c_str(), cfg1.c_str(), h->last_cigar_lanes);
+	return AT_OK;
+}
+
+extern "C" int at_scan(at_handle *h,
+                       int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+                       int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+                       int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile_cols, int flags,
+                       int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
+                       int32_t *out_state, int32_t *out_strand, int32_t *out_nhits,
+                       int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
+                       uint32_t *out_cigar, int64_t cigar_cap)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_scan: NULL handle");
+	if (nq < 0 || nt < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "at_scan: negative size");
+	if (k < 1 || k > 64) return fail(h, AT_ERR_ARG, "at_scan: k = %d outside 1..64", k);
+	if (strands < AT_STRAND_FWD || strands > AT_STRAND_BOTH) return fail(h, AT_ERR_ARG, "at_scan: strands = %d outside 1..3", strands);
+	if (tile_cols < 0 || (tile_cols & 15))
+		return fail(h, AT_ERR_ARG, "at_scan: tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)", tile_cols, at::kScanDefaultTile);
+	if (flags & ~AT_CIGAR_M) return fail(h, AT_ERR_ARG, "at_scan: flags = %d (AT_CIGAR_M or 0)", flags);
+	const bool rev = strands != AT_STRAND_FWD;
+	const bool cg = out_stats || out_ncigar || out_cigar_off || out_cigar;
+	if (cg && (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)))
+		return fail(h, AT_ERR_ARG, "at_scan: the CIGAR outputs are either all NULL or all given");
+	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "at_scan: %lld queries + %lld targets: at most 2^31 - 1 reads", (long long)nq, (long long)nt);
+	if (rev && (nt >= (1LL << 30) || 2 * nq + nt >= (1LL << 31)))
+		return fail(h, AT_ERR_ARG, "at_scan: %lld queries, %lld targets: a reverse strand needs nt < 2^30 and 2 nq + nt < 2^31", (long long)nq, (long long)nt);
+	if (h->comm) return fail(h, AT_ERR_DOMAIN, "at_scan: one GPU only (this handle belongs to a multi-process job)");
+	if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "at_scan needs the unit mismatch cost: u = %d, not 1", h->u);
+	if (nq == 0) return AT_OK;
+	if (!q_blob || !q_off || !q_len || !out_target || !out_score || !out_end_i || !out_end_j || !out_state || !out_nhits ||
+	    (rev && !out_strand) || (nt > 0 && (!t_blob || !t_off || !t_len)))
+		return fail(h, AT_ERR_ARG, "at_scan: NULL argument");
+	int32_t maxq = 0;
+	for (int64_t q = 0; q < nq; ++q) {
+		if (q_len[q] < 0 || q_off[q] < 0) return fail(h, AT_ERR_ARG, "query %lld: negative length or offset", (long long)q);
+		if (q_len[q] > at::kScanMaxQuery) return fail(h, AT_ERR_DOMAIN, "at_scan: query %lld has %d bases, more than %d", (long long)q, q_len[q], at::kScanMaxQuery);
+		maxq = std::max(maxq, q_len[q]);
+	}
+	for (int64_t t = 0; t < nt; ++t)
+		if (t_len[t] < 0 || t_off[t] < 0) return fail(h, AT_ERR_ARG, "target %lld: negative length or offset", (long long)t);
+	const int32_t tile = tile_cols > 0 ? tile_cols : at::kScanDefaultTile;
+	return guarded(h, "at_scan", [&]() -> int {
+		for (int64_t e = 0; e < nq * k; ++e) { out_target[e] = -1; out_score[e] = 0; out_end_i[e] = 0; out_end_j[e] = 0; out_state[e] = 0; }
+		if (out_strand) for (int64_t e = 0; e < nq * k; ++e) out_strand[e] = -1;
+		for (int64_t q = 0; q < nq; ++q) out_nhits[q] = 0;
+		if (cg) {
+			for (int64_t e = 0; e < nq * k; ++e) { out_ncigar[e] = 0; for (int x = 0; x < 8; ++x) out_stats[e * 8 + x] = -1; }
+			for (int64_t e = 0; e <= nq * k; ++e) out_cigar_off[e] = 0;
+		}
+		if (nt == 0) {
+			snprintf(h->cfg, sizeof h->cfg, "scan: tile=%d overlap<=0 groups=0 k=%d strands=%s, 0 blocks, 0 slices; ", tile, k, scan_strands_text(strands));
+			return (int)AT_OK;
+		}
+		int64_t bytes = 0;
+		for (int64_t q = 0; q < nq; ++q) bytes += q_len[q];
+		for (int64_t t = 0; t < nt; ++t) bytes += t_len[t];
+		std::vector<uint8_t> blob((size_t)bytes + 32);
+		std::vector<int64_t> off((size_t)(nq + nt));
+		std::vector<int32_t> len((size_t)(nq + nt));
+		int64_t at = 0;
+		for (int64_t r = 0; r < nq + nt; ++r) {
+			const bool isq = r < nq;
+			const int32_t l = isq ? q_len[r] : t_len[r - nq];
+			if (l) memcpy(blob.data() + at, isq ? q_blob + q_off[r] : t_blob + t_off[r - nq], (size_t)l);
+			off[(size_t)r] = at; len[(size_t)r] = l; at += l;
+		}
+		ReadSet rs;
+		int rc = upload_reads(h, AT_MODE_EDIT, nq + nt, blob.data(), off.data(), len.data(), &rs, rev ? nq : 0);
+		if (rc) return rc;
+		if (rs.bits != 2) return fail(h, AT_ERR_DOMAIN, "at_scan needs 2-bit reads: some base of a query or a target is not one of ACGT");
+		size_t bkey = 0, bl4 = 0;
+		rc = scan_lists(h, nq, q_len, nt, t_len, rs, k, use_cutoff, cutoff, strands, tile, out_target, out_score, out_end_i, out_end_j, out_state,
+		                out_strand, out_nhits, &bkey, &bl4);
+		if (rc || !cg) return rc;
+		return scan_cigars(h, nq, k, strands, rs, nt, maxq, bkey, bl4, out_target, out_score, out_end_i, out_end_j, flags, out_stats, out_ncigar,
+		                   out_cigar_off, out_cigar, cigar_cap);
+	});
 }
 
 /* ---- reverse complement: the host helper and the device entry (the kernel: at_revcomp.hip) ---- */

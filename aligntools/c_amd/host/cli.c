@@ -153,6 +153,9 @@ static int main_single(int cmd, int argc, char *argv[])
  *                    the read may start and end anywhere in the target); the formats stay, the values are the infix ones -- with
  *                    --alignments --paf the target start and end columns are where the match lies.  Also on --queries, whose hits
  *                    then rank by where the read fits.  Not with --all-vs-all, --gpus N > 1.
+ *     --scan         (edit -u 1 --infix --queries, with --score-only or --paf) reads against LONG targets (at_scan): the hits of the
+ *                    --queries form with no bound on the target length; --score-only prints their hit lines, --paf their PAF lines
+ *                    (target start and end absolute, cg:Z the =/X CIGAR).  Not with --all-vs-all, --gpus N > 1.
  *     --gpus N       one process per GPU: this process starts N workers (itself, with AT_RANK / AT_WORLD / AT_DEVICE /
  *                    AT_COMM_DIR in their environment), rank 0's options are broadcast over RCCL, every rank aligns a
  *                    contiguous share of the pairs on its own GPU, results are gathered over RCCL and rank 0 prints them
@@ -161,7 +164,7 @@ static int main_single(int cmd, int argc, char *argv[])
  * thread -- which also pays the HIP start-up, in the shadow of the first chunks' parsing -- sends each chunk to the GPU
  * and writes its results with one fwrite.  Memory is bounded by the chunks in flight, whatever the size of the file;
  * --all-vs-all keeps the read set and streams slices of the triangle instead (at_align_allpairs_stream). */
-typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments, infix; } batch_flags;
+typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments, infix, scan; } batch_flags;
 static int g_edit_alignments;   /* --alignments: every handle of this process delivers edit alignments (set before any handle exists) */
 static int g_edit_infix;        /* --infix: every handle of this process is in edit infix mode (at_set_edit_infix; set likewise) */
 
@@ -764,6 +767,74 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 	return 0;
 }
 
+/* ---- --scan (edit -u 1 --infix --queries): reads against long targets, the best K hits of each query (at_scan) ----
+ * --score-only prints the hit lines of the --queries form, --paf its PAF lines; the CIGARs come with the hits, from the same call. */
+static int batch_scan(opt_t *opt, const batch_flags *bf, const char *qfile, const char *tfile)
+{
+	at_reader *rq = at_reader_open(qfile), *rt;
+	at_chunk c;
+	at_handle *h;
+	tbuf out = {NULL, 0, 0};
+	int64_t nq, nt, q, x, n, *qoff, *toff, *cgoff = NULL, cap = 0;
+	int32_t *qlen, *tlen, *tgt, *sc, *ei, *ej, *st, *nh, *sd, *stats = NULL, *ncg = NULL;
+	uint32_t *cg = NULL;
+	int rc, j, pass;
+	const int kb = bf->best;
+	if (!rq) die("Can't open %s\n", qfile);
+	rt = at_reader_open(tfile);
+	if (!rt) die("Can't open %s\n", tfile);
+	memset(&c, 0, sizeof c);
+	while (at_reader_read(rq, (size_t)-1, (size_t)-1, &c) > 0) {}
+	nq = (int64_t)c.n;
+	while (at_reader_read(rt, (size_t)-1, (size_t)-1, &c) > 0) {}
+	nt = (int64_t)c.n - nq;
+	at_reader_close(rq); at_reader_close(rt);
+	if (nq == 0 || nt == 0) { at_chunk_free(&c); return 0; }
+	h = at_host_handle();
+	rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, 0, NULL, 0);
+	if (rc != AT_OK) die("%s", at_last_error(h));
+	n = nq * kb;
+	qoff = (int64_t *)at_xmalloc((size_t)nq * 8); qlen = (int32_t *)at_xmalloc((size_t)nq * 4);
+	toff = (int64_t *)at_xmalloc((size_t)nt * 8); tlen = (int32_t *)at_xmalloc((size_t)nt * 4);
+	for (q = 0; q < nq; ++q) { qoff[q] = (int64_t)c.off[q]; qlen[q] = (int32_t)c.len[q]; }
+	for (x = 0; x < nt; ++x) { toff[x] = (int64_t)c.off[nq + x]; tlen[x] = (int32_t)c.len[nq + x]; }
+	tgt = (int32_t *)at_xmalloc((size_t)n * 4); sc = (int32_t *)at_xmalloc((size_t)n * 4);
+	ei = (int32_t *)at_xmalloc((size_t)n * 4); ej = (int32_t *)at_xmalloc((size_t)n * 4);
+	st = (int32_t *)at_xmalloc((size_t)n * 4); sd = (int32_t *)at_xmalloc((size_t)n * 4); nh = (int32_t *)at_xmalloc((size_t)nq * 4);
+	if (bf->paf) {
+		stats = (int32_t *)at_xmalloc((size_t)n * 32); ncg = (int32_t *)at_xmalloc((size_t)n * 4);
+		cgoff = (int64_t *)at_xmalloc((size_t)(n + 1) * 8);
+		cap = 16 * n + 64;
+	}
+	trace("scan: records read, queries", nq);
+	for (pass = 0; pass < 2; ++pass) {       /* a second call if the hits have more runs than the first guess */
+		if (bf->paf) { free(cg); cg = (uint32_t *)at_xmalloc((size_t)cap * 4); }
+		rc = at_scan(h, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, 0, 0, bf->both ? AT_STRAND_BOTH : AT_STRAND_FWD, 0, 0,
+		             tgt, sc, ei, ej, st, sd, nh, stats, ncg, cgoff, cg, cap);
+		if (rc != AT_OK) die("%s", at_last_error(h));
+		if (!bf->paf || cgoff[n] <= cap) break;
+		cap = cgoff[n];
+	}
+	trace("scan: done, queries", nq);
+	for (q = 0; q < nq; ++q) {
+		for (j = 0; j < nh[q]; ++j) {
+			const int64_t e = q * kb + j;
+			const char strand = sd[e] == 1 ? '-' : '+';
+			if (bf->paf)
+				tb_paf(&out, c.names + c.name_off[q], qlen[q], strand, c.names + c.name_off[nq + tgt[e]], tlen[tgt[e]], -sc[e], ei[e], ej[e],
+				       stats + 8 * e, cg + cgoff[e], ncg[e]);
+			else
+				tb_pair_strand(&out, c.names + c.name_off[q], c.names + c.name_off[nq + tgt[e]], sc[e], 1, bf->both ? strand : 0, NULL, NULL, 0);
+		}
+		if (out.l > ((size_t)8 << 20)) tb_flush(&out);
+	}
+	tb_flush(&out);
+	free(out.s); free(qoff); free(qlen); free(toff); free(tlen); free(tgt); free(sc); free(ei); free(ej); free(st); free(sd); free(nh);
+	free(stats); free(ncg); free(cgoff); free(cg);
+	at_chunk_free(&c);
+	return 0;
+}
+
 /* start one worker per GPU (this binary again, told its rank through the environment) and wait for them */
 static int batch_launch(int world, char *argv0, int argc, char *argv[])
 {
@@ -823,10 +894,10 @@ static int main_batch(int argc, char *argv[], char *argv0)
 {
 	int cmd = -1, k, n = 0;
 	opt_t *opt = init_opt();
-	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0, 0};
+	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0, 0, 0};
 	char **av = (char **)at_xmalloc((size_t)(argc + 1) * sizeof(char *));
-	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] [--paf] [--alignments] [--infix] <pairs.fa>\n"
-	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] [--infix] <targets.fa>\n";
+	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] [--paf] [--alignments] [--infix] [--scan] <pairs.fa>\n"
+	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] [--infix] [--scan] <targets.fa>\n";
 	/* the long flags of the extension are taken out before getopt sees the reference's short options */
 	for (k = 0; k < argc; ++k) {
 		if (strcmp(argv[k], "--score-only") == 0) bf.score_only = 1;
@@ -839,6 +910,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (strcmp(argv[k], "--paf") == 0) bf.paf = 1;
 		else if (strcmp(argv[k], "--alignments") == 0) bf.alignments = 1;
 		else if (strcmp(argv[k], "--infix") == 0) bf.infix = 1;
+		else if (strcmp(argv[k], "--scan") == 0) bf.scan = 1;
 		else av[n++] = argv[k];
 	}
 	av[n] = NULL;
@@ -848,7 +920,12 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	/* --queries: refused with what it cannot go with, before any GPU call */
 	{
 		const char *why = NULL;
-		if (bf.queries && bf.all_vs_all) why = "--queries does not go with --all-vs-all (a search aligns queries against targets)";
+		if (bf.scan && !bf.infix) why = "--scan goes with edit -u 1 --infix";
+		else if (bf.scan && bf.all_vs_all) why = "--scan does not go with --all-vs-all";
+		else if (bf.scan && !bf.queries) why = "--scan goes with --queries (reads against long targets)";
+		else if (bf.scan && bf.gpus > 1) why = "--scan runs on one GPU: it does not go with --gpus N > 1";
+		else if (bf.scan && !bf.score_only && !bf.paf) why = "--scan needs --score-only or --paf";
+		else if (bf.queries && bf.all_vs_all) why = "--queries does not go with --all-vs-all (a search aligns queries against targets)";
 		else if (bf.queries && bf.gpus > 1) why = "--queries runs on one GPU: it does not go with --gpus N > 1";
 		else if (bf.queries && bf.min_on && cmd == C_EDIT) why = "--min-score does not go with `batch edit --queries` (edit ranks by distance)";
 		else if (bf.best_set && !bf.queries) why = "--best goes with --queries";
@@ -861,7 +938,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (bf.infix && cmd != C_EDIT) why = "--infix goes with edit";
 		else if (bf.infix && bf.all_vs_all) why = "--infix does not go with --all-vs-all";
 		else if (bf.infix && bf.gpus > 1) why = "--infix runs on one GPU: it does not go with --gpus N > 1";
-		else if (bf.paf && cmd == C_EDIT && !bf.alignments) why = "--paf does not go with edit (edit has no alignment)";
+		else if (bf.paf && cmd == C_EDIT && !bf.alignments && !bf.scan) why = "--paf does not go with edit (edit has no alignment)";
 		else if (bf.paf && bf.score_only) why = "--paf does not go with --score-only (a PAF line needs the traceback)";
 		else if (bf.paf && bf.all_vs_all) why = "--paf does not go with --all-vs-all";
 		else if (bf.paf && bf.gpus > 1) why = "--paf runs on one GPU: it does not go with --gpus N > 1";
@@ -877,7 +954,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	g_edit_alignments = bf.alignments;
 	g_edit_infix = bf.infix;
 	if (bf.queries) {
-		k = batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
+		k = bf.scan ? batch_scan(opt, &bf, bf.queries, av[n - 1]) : batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
 		free(opt->sites.pos); free(opt); free(av);
 		return k;
 	}

@@ -387,6 +387,42 @@ int at_align_batch_cigar(at_handle *h, int mode, int64_t npairs,
                          uint32_t *out_cigar, int64_t cigar_cap);
 
 /*
+ * Reads against LONG targets: what at_search_strands delivers under at_set_edit_infix -- for each query the best
+ * k hits (1 <= k <= 64) over the targets, a hit being the best match of the query (or of its reverse complement) INSIDE a target:
+ * D(0,j) = 0, D(i,0) = i, score = min over j of D(l1,j), end cell (l1, j*) with the smallest such j, state AT_ST_MID -- with no
+ * bound on the target length (any int32).  A target is cut into overlapping tiles that are swept independently; the minimum over
+ * the tiles is exact for every pair that scores <= the query length (with use_cutoff: <= min(query length, cutoff); the other
+ * pairs are no hits anyway).  Queries of up to 1 024 bases, pure ACGT, u == 1; one GPU.
+ *   rank: smaller distance first, then the smaller target index, then strand 0 before strand 1
+ *   out_target .. out_nhits as in at_search_strands (nq*k entries, unused entries -1; out_strand may be NULL for AT_STRAND_FWD);
+ *   end_j is the ABSOLUTE column j* of the target
+ *   tile_cols: the columns a lane owns, a multiple of 16; 0 = the library's default (2 048).  The results do not depend on it
+ *   the four CIGAR outputs are either all NULL or laid out as in at_align_batch_cigar over the nq*k entries (out_cigar_off has
+ *   nq*k + 1 entries; an unused entry has 0 runs and a statistics row of -1; flags: AT_CIGAR_M or 0).  The ops of a hit are those of
+ *   the three-way rule above on the full table; AT_CG_START_J is absolute.  They are made in a window of the target around the hit
+ *   (at most 2 * 1 024 + 15 columns), and a window that does not reproduce its hit is AT_ERR_RANGE, never a silent result
+ * The handle's at_set_edit_infix / at_set_edit_traceback settings neither matter nor change.  Synchronous.  nq == 0 writes
+ * nothing; nt == 0 gives every query 0 hits.  AT_ERR_DOMAIN: u != 1, a byte outside ACGT, a query longer than 1 024, a handle of a
+ * multi-process job; AT_ERR_ARG: k outside 1..64, strands outside 1..3, tile_cols negative or no multiple of 16.
+ * at_last_config: "scan: tile=T overlap<=OV groups=G k=K strands=fwd|rev|both, B blocks, S slices; myers-scan bits=2 words/lane=W ..."
+ * and, with CIGARs, "; windows: " and the window pass's text.
+ */
+int at_scan(at_handle *h,
+            int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+            int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+            int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile_cols, int flags,
+            int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
+            int32_t *out_state, int32_t *out_strand, int32_t *out_nhits,
+            int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
+            uint32_t *out_cigar, int64_t cigar_cap);
+/* Host helper (no handle, no GPU): how at_scan cuts a pair of len1 x len2 -- *tile = the columns a lane owns (tile_cols, or the
+ * default for 0), *overlap = the warm-up columns in front of a tile, round16up(len1 + c) with c = len1 without a cutoff and
+ * min(len1, cutoff) with one, *ngroups = ceil(len2 / (64 * tile)), at least 1.  Any out pointer may be NULL.  AT_ERR_ARG for a
+ * negative length and for a tile_cols that is negative or no multiple of 16. */
+int at_scan_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutoff, int32_t tile_cols,
+                 int32_t *tile, int32_t *overlap, int64_t *ngroups);
+
+/*
  * Multi-process batches: one process per GPU, each with its own handle.  The pairs are independent, so
  * the only communication is a broadcast of rank 0's scoring block and a gather of results, both RCCL collectives on the
  * handles' devices (over xGMI inside a node).  `dir` is a directory all ranks can reach: rank 0 leaves the RCCL id there.
