@@ -26,12 +26,13 @@ CIGAR_M = 1                     # AT_CIGAR_M: '=' and 'X' merge into 'M'
 CIGAR_LETTERS = b"MIDNSHP=X"    # a CIGAR word is (run length << 4) | index into this
 ERR_ARG, ERR_DOMAIN = -1, -4
 ST_LOW, ST_MID, ST_UPP = 1, 2, 3
+SCAN_SEP_READ = -1              # AT_SCAN_SEP_READ: min_sep of Aligner.scan_hits = each query's own length
 
 # every symbol include/aligntools_hip.h declares
 ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_set_edit_traceback", "at_set_edit_infix", "at_align_batch",
                "at_align_batch_device", "at_align_allpairs_device", "at_render_batch_device", "at_compact_ops_device",
                "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream", "at_search",
-               "at_search_strands", "at_scan", "at_scan_plan", "at_revcomp", "at_revcomp_device",
+               "at_search_strands", "at_scan", "at_scan_plan", "at_scan_hits", "at_revcomp", "at_revcomp_device",
                "at_cigar", "at_cigar_batch_device", "at_align_batch_cigar",
                "at_comm_init", "at_comm_broadcast_scoring", "at_comm_allgather", "at_comm_destroy", "at_comm_abi_checked",
                "at_pack_words", "at_pack_batch", "at_render", "at_last_config"]
@@ -135,6 +136,9 @@ def load_library():
     lib.at_scan.restype = C.c_int
     lib.at_scan.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_int, C.c_int, C.c_int32, C.c_int, C.c_int32, C.c_int] + [C.c_void_p] * 11 + [C.c_int64]
+    lib.at_scan_hits.restype = C.c_int
+    lib.at_scan_hits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int64, C.c_int, C.c_int64] + [C.c_void_p] * 9 + [C.c_int64]
     lib.at_scan_plan.restype = C.c_int
     lib.at_scan_plan.argtypes = [C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int32, _i32p, _i32p, _i64p]
     lib.at_revcomp.restype = C.c_int
@@ -569,6 +573,59 @@ class Aligner:
             out["cigar"] = [[words[cigar_off[q * kk + e]:cigar_off[q * kk + e] + max(int(ncigar[q, e]), 0)].copy() for e in range(kk)]
                             for q in range(nq)]
         return out
+
+    def scan_hits(self, queries, targets, max_dist, min_sep=SCAN_SEP_READ, strands="forward", cigar=False, cigar_m=False, tile_cols=0,
+                  cand_cap=0):
+        """Every occurrence of every query in every target with at most `max_dist` edits (at_scan_hits): the leftmost column of each
+        strict local minimum of the last row of scan()'s table that is <= min(max_dist, len(query) - 1).  min_sep > 0 keeps an
+        occurrence only if no other occurrence of the same (query, strand, target) within min_sep columns is better -- smaller
+        distance, then smaller column; 0 keeps all; SCAN_SEP_READ (-1, the default) stands for each query's own length.
+        Returns a dict: hit_off (nq + 1,) int64 -- the hits of query q are the entries hit_off[q] .. hit_off[q + 1] -- and target,
+        score, end_j (the absolute end column), strand (0 / 1), int32 arrays over the hits, a query's hits by (distance, target,
+        strand, column); with cigar=True also stats (nhits, 8), ncigar (nhits,) and cigar, a list of numpy uint32 arrays
+        ('=' / 'X'; cigar_m: 'M').  tile_cols and cand_cap (the candidate records a slice may leave on the device; 0: the default)
+        do not change the results."""
+        if strands not in STRANDS:
+            raise ValueError("strands must be one of %s" % ", ".join(sorted(STRANDS)))
+        qs = [_b(x) for x in queries]
+        ts = [_b(x) for x in targets]
+        nq, nt = len(qs), len(ts)
+
+        def pack(seqs):
+            lens = np.fromiter((len(x) for x in seqs), dtype=np.int32, count=len(seqs))
+            off = np.zeros(len(seqs), dtype=np.int64)
+            if len(seqs) > 1:
+                np.cumsum(lens[:-1], out=off[1:])
+            return np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8).copy(), off, lens
+        qb, qo, ql = pack(qs)
+        tb, to, tl = pack(ts)
+        hit_off = np.zeros(nq + 1, dtype=np.int64)
+        hit_cap, cap = 4 * nq + 64, 0
+        for _ in range(3):                                      # more hits, then more runs, than the first guess has room for
+            out = {name: np.zeros(hit_cap, dtype=np.int32) for name in ("target", "score", "end_j", "strand")}
+            stats = np.full((hit_cap, 8), -1, dtype=np.int32) if cigar else None
+            ncigar = np.zeros(hit_cap, dtype=np.int32) if cigar else None
+            cigar_off = np.zeros(hit_cap + 1, dtype=np.int64) if cigar else None
+            cap = max(cap, 16 * hit_cap + 64)
+            words = np.zeros(cap, dtype=np.uint32) if cigar else None
+            self._check(self._lib.at_scan_hits(self._h, nq, _ptr(qb), _ptr(qo), _ptr(ql), nt, _ptr(tb), _ptr(to), _ptr(tl), int(max_dist),
+                                               int(min_sep), STRANDS[strands], int(tile_cols), int(cand_cap), CIGAR_M if cigar_m else 0,
+                                               hit_cap, _ptr(hit_off), _ptr(out["target"]), _ptr(out["score"]), _ptr(out["end_j"]),
+                                               _ptr(out["strand"]), _ptr(stats), _ptr(ncigar), _ptr(cigar_off), _ptr(words),
+                                               cap if cigar else 0))
+            n = int(hit_off[nq])
+            if n > hit_cap:
+                hit_cap = n
+                continue
+            if not cigar or cigar_off[n] <= cap:
+                break
+            cap = int(cigar_off[n])
+        res = {name: a[:n].copy() for name, a in out.items()}
+        res["hit_off"] = hit_off
+        if cigar:
+            res["stats"], res["ncigar"], res["cigar_off"] = stats[:n].copy(), ncigar[:n].copy(), cigar_off[:n + 1].copy()
+            res["cigar"] = [words[cigar_off[e]:cigar_off[e] + max(int(ncigar[e]), 0)].copy() for e in range(n)]
+        return res
 
     def align_allpairs_device(self, mode, nreads, d_seq, bits, d_woff, d_len, max_len, first_pair, npairs, want_traceback,
                               d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream=0):

@@ -16,6 +16,7 @@
 #include "at_edit_tb.hip.h"
 #include "at_infix.hip.h"
 #include "at_scan.hip.h"
+#include "at_scanhits.hip.h"
 #include "../../../include/aligntools_hip.h"
 
 #include <algorithm>
@@ -100,6 +101,7 @@ struct at_handle {
 	int min_on = 0, min_score = 0;  /* at_set_min_score: all-vs-all overlap scores skip pairs proven below it */
 	int edit_tb = 0;                /* at_set_edit_traceback: edit batches with want_traceback deliver their ops (at_edit_tb.hip.h) */
 	int edit_infix = 0;             /* at_set_edit_infix: AT_MODE_EDIT is the best match of s1 inside s2 (at_infix.hip.h) */
+	int infix_anchor = 0;           /* inside at_scan_hits' window pass only: infix alignments end in (l1, l2) (InfixArgs::anchor_end) */
 	/* device scratch (grow-only) */
 	uint32_t *d_sitemask = nullptr; size_t sitemask_words = 0; int sitemask_for_l2 = -1; bool sitemask_dirty = true;
 	uint32_t *d_ws = nullptr; size_t ws_bytes = 0;
@@ -115,6 +117,8 @@ struct at_handle {
 	void *d_order = nullptr; size_t order_bytes = 0;
 	void *d_str = nullptr; size_t str_bytes = 0;
 	void *d_scan = nullptr; size_t scan_bytes = 0;
+	void *d_cand = nullptr; size_t cand_bytes = 0;       /* at_scan_hits: a slice's candidates and what the selection makes of them */
+	void *d_sorttmp = nullptr; size_t sorttmp_bytes = 0; /* ... the radix sort's scratch */
 	int *d_rflag = nullptr;         /* at_render_k's "op list walks off its sequences" flag */
 	/* host entry: page-locked staging -- descriptor block, raw bytes on their way up, results and payload on their way down */
 	void *hp_desc = nullptr; size_t hp_desc_bytes = 0;
@@ -267,6 +271,8 @@ extern "C" void at_destroy(at_handle *h)
 	if (h->d_order) (void)hipFree(h->d_order);
 	if (h->d_str) (void)hipFree(h->d_str);
 	if (h->d_scan) (void)hipFree(h->d_scan);
+	if (h->d_cand) (void)hipFree(h->d_cand);
+	if (h->d_sorttmp) (void)hipFree(h->d_sorttmp);
 	if (h->d_rflag) (void)hipFree(h->d_rflag);
 	if (h->d_cg) (void)hipFree(h->d_cg);
 	if (h->hp_cg) (void)hipHostFree(h->hp_cg);
@@ -1066,6 +1072,7 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		}
 		ia.ops = d_ops; ia.ops_off = (const long long *)d_ops_off;
 		ia.slab = h->d_ws; ia.slab_words = slab_words;
+		ia.anchor_end = h->infix_anchor;
 		if (int rcq = ensure_queue(h, stream)) return rcq;
 		ia.m.queue = h->d_queue;
 		hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, stream, ia);
@@ -2600,12 +2607,17 @@ static int scan_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64_t nt
 }
 
 /* the alignments of the hits: every list entry as a window pair through at_infix<W, true> and the CIGAR kernels (at_scan.hip.h) */
+/* at_scan: the n = nq * k list entries, entry e of query e / k, windows that end in their arg-min.  at_scan_hits (who names the caller
+ * in an error text): n hits with their queries in d_eq and END-ANCHORED windows -- a hit that is not the best of its triple is not the
+ * arg-min of its window */
 static int scan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadSet &rs, int64_t nt, int32_t maxq, size_t bkey, size_t bl4,
                        const int32_t *out_target, const int32_t *out_score, const int32_t *out_end_i, const int32_t *out_end_j, int flags,
-                       int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap)
+                       int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap,
+                       int64_t nhits = -1, const int *d_eq = nullptr, const char *who = "at_scan")
 {
 	const int enc = strands != AT_STRAND_FWD;
-	const int64_t n = nq * k;
+	const int64_t n = nhits >= 0 ? nhits : nq * k;
+	const int anchor = nhits >= 0 ? 1 : 0;
 	/* ops slots: l1 + window columns per hit, back to back */
 	std::vector<int64_t> slot((size_t)n);
 	int64_t ops_bytes = 0;
@@ -2642,7 +2654,7 @@ static int scan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadS
 	at::ScanWindowArgs wa;
 	memset(&wa, 0, sizeof wa);
 	wa.n = n; wa.k = k; wa.nq = (int)nq; wa.enc = enc; wa.nrev0 = (int)(nq + nt);
-	wa.lkey = (const unsigned long long *)dl; wa.lej = (const int *)(dl + bkey + bl4);
+	wa.lkey = (const unsigned long long *)dl; wa.lej = (const int *)(dl + bkey + bl4); wa.eq = d_eq;
 	wa.swoff = (const long long *)rs.d_swoff; wa.slen = rs.d_len;
 	wa.woff1 = (long long *)d_woff1; wa.woff2 = (long long *)d_woff2; wa.len1 = d_len1; wa.len2 = d_len2; wa.ws = d_ws;
 	wa.w_score = d_sc; wa.w_end_j = d_ej; wa.ncigar = d_ncigar; wa.stats = d_stats; wa.ncigar_out = d_ncout; wa.bad = d_bad;
@@ -2651,10 +2663,10 @@ static int scan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadS
 	{
 		/* the window pass is an infix batch with op lists whatever the handle's settings say; they are put back at once */
 		const int keep_infix = h->edit_infix, keep_tb = h->edit_tb;
-		h->edit_infix = 1; h->edit_tb = 1;
+		h->edit_infix = 1; h->edit_tb = 1; h->infix_anchor = anchor;
 		rc = align_device(h, AT_MODE_EDIT, n, rs.d_words, 2, d_woff1, d_len1, d_woff2, d_len2, maxq, max2, 0, 1, d_sc, d_ei, d_ej, d_st,
 		                  d_ops, d_ops_off, d_nops, s, 0, 0);
-		h->edit_infix = keep_infix; h->edit_tb = keep_tb;
+		h->edit_infix = keep_infix; h->edit_tb = keep_tb; h->infix_anchor = 0;
 	}
 	if (rc) { (void)hipStreamSynchronize(s); return rc; }
 	const std::string cfg1 = h->cfg;
@@ -2668,7 +2680,7 @@ static int scan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadS
 	HIP_TRY(h, hipMemcpyAsync(out_stats, d_stats, (size_t)n * 32, hipMemcpyDeviceToHost, s));
 	HIP_TRY(h, hipMemcpyAsync(out_cigar_off, d_coff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
 	HIP_TRY(h, hipStreamSynchronize(s));
-	if (bad) return fail(h, AT_ERR_RANGE, "at_scan: a hit's window does not reproduce its score and end column (target columns [ws, j*) of at most %d)", max2);
+	if (bad) return fail(h, AT_ERR_RANGE, "%s: a hit's window does not reproduce its score and end column (target columns [ws, j*) of at most %d)", who, max2);
 	/* the words of the entries that end within the caller's capacity: a prefix of the device buffer */
 	int64_t fit = 0;
 	for (int64_t e = 0; e < n; ++e) if (out_cigar_off[e + 1] <= cigar_cap) fit = out_cigar_off[e + 1]; else break;
@@ -2753,6 +2765,315 @@ extern "C" int at_scan(at_handle *h,
 		if (rc || !cg) return rc;
 		return scan_cigars(h, nq, k, strands, rs, nt, maxq, bkey, bl4, out_target, out_score, out_end_i, out_end_j, flags, out_stats, out_ncigar,
 		                   out_cigar_off, out_cigar, cigar_cap);
+	});
+}
+
+/* ---- every occurrence of a read under a distance cutoff (at_scan_hits; at_scanhits.hip.h) ---- */
+struct ScanHitsRun {
+	long long cand = 0, kept = 0, resweeps = 0, nslices = 0, nblocks = 0, gall = 0;
+	int ov_most = 0;
+	double sweep_ms = 0.0, select_ms = 0.0;
+	std::string cfg0;
+};
+
+/* the hits of at_scan_hits in their final order and the hits of each query: the blocks and slices of scan_lists; per slice the groups
+ * of its pairs are swept by at_scan<W, true> (once more into a buffer of the counted size if the candidates did not fit), the
+ * candidates sorted, marked and compacted on the device (at_scanhits.hip.h) and the kept ones fetched */
+static int scan_hits_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64_t nt, const int32_t *t_len, const ReadSet &rs,
+                           int32_t max_dist, int32_t min_sep, int strands, int32_t tile, int64_t cand_cap,
+                           std::vector<at::ScanHit> &hits, std::vector<int32_t> &qcount, ScanHitsRun &run)
+{
+	const int enc = strands != AT_STRAND_FWD, two = strands == AT_STRAND_BOTH;
+	const int64_t nv = nq << two;
+	std::vector<int> qs((size_t)nq), qperm((size_t)nv);
+	for (int64_t q = 0; q < nq; ++q) qs[(size_t)q] = (int)q;
+	std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
+	for (int64_t q = 0; q < nq; ++q) {
+		const int c = qs[(size_t)q];
+		if (two) { qperm[(size_t)(2 * q)] = c << 1; qperm[(size_t)(2 * q + 1)] = (c << 1) | 1; }
+		else qperm[(size_t)q] = enc ? (c << 1) | 1 : c;
+	}
+	std::vector<long long> gpre((size_t)nt + 1);
+	gpre[0] = 0;
+	int64_t tsum = 0;
+	for (int64_t t = 0; t < nt; ++t) {
+		gpre[(size_t)t + 1] = gpre[(size_t)t] + at::scan_groups(t_len[t], tile);
+		tsum += t_len[t];
+	}
+	const long long gall = gpre[(size_t)nt];
+	struct Block { int qa, nqb; int32_t l1; };
+	std::vector<Block> blocks;
+	int64_t most = 0;
+	for (int64_t a = 0, b; a < nq; a = b) {
+		const int32_t L = q_len[qs[(size_t)a]];
+		for (b = a; b < nq && q_len[qs[(size_t)b]] == L; ++b) {}
+		if (L < 1) continue;                                   /* a query of length 0 has no hits */
+		blocks.push_back({(int)(a << two), (int)((b - a) << two), L});
+		most = std::max<int64_t>(most, ((b - a) << two) * nt);
+	}
+	int64_t chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
+	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(std::max<int64_t>(most, 1), 1LL << 28)));
+	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	const size_t bq = al((size_t)nv * 4), bg = al(((size_t)nt + 1) * 8), bc = al((size_t)nq * 4);
+	int rc = grow(h, &h->d_desc, &h->desc_bytes, 256 + bg + bq + bc);
+	if (rc) return rc;
+	char *dd = (char *)h->d_desc;
+	unsigned long long *d_ncand = (unsigned long long *)dd;
+	long long *d_gpre = (long long *)(dd + 256);
+	int *d_qperm = (int *)(dd + 256 + bg), *d_qcount = (int *)(dd + 256 + bg + bq);
+	hipStream_t s = h->stream;
+	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nv * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_gpre, gpre.data(), ((size_t)nt + 1) * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemsetAsync(d_qcount, 0, (size_t)nq * 4, s));
+	/* the candidate block of a capacity: keys and values before and behind the sort, flags, prefix sums, hit records */
+	struct Cand { unsigned long long *k0, *k1; long long *off; int *v0, *v1, *flag; at::ScanHit *hit; };
+	auto cand_bytes = [&](int64_t cap) { return 2 * al((size_t)cap * 8) + al(((size_t)cap + 1) * 8) + 3 * al((size_t)cap * 4) + al((size_t)cap * sizeof(at::ScanHit)); };
+	auto cand_at = [&](int64_t cap) {
+		char *p = (char *)h->d_cand;
+		Cand c;
+		c.k0 = (unsigned long long *)p; p += al((size_t)cap * 8);
+		c.k1 = (unsigned long long *)p; p += al((size_t)cap * 8);
+		c.off = (long long *)p; p += al(((size_t)cap + 1) * 8);
+		c.v0 = (int *)p; p += al((size_t)cap * 4);
+		c.v1 = (int *)p; p += al((size_t)cap * 4);
+		c.flag = (int *)p; p += al((size_t)cap * 4);
+		c.hit = (at::ScanHit *)p;
+		return c;
+	};
+	struct Ev { hipEvent_t e[3] = {nullptr, nullptr, nullptr}; ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
+	for (hipEvent_t &x : ev.e) HIP_TRY(h, hipEventCreate(&x));
+	auto items_before = [&](int64_t x) { return (long long)(x / nt) * gall + gpre[(size_t)(x % nt)]; };
+	run.gall = gall; run.nblocks = (long long)blocks.size();
+	for (const Block &B : blocks) {
+		const int64_t bp = (int64_t)B.nqb * nt;
+		const int w = at::class_rows(at::kMyersLaneWords, B.l1);
+		const void *fn = at_scan_hits_kernel(w);
+		if (!fn) return fail(h, AT_ERR_ARG, "no scan kernel for %d words per lane", w);
+		int occ = 0;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64, 0) != hipSuccess || occ <= 0) occ = 8;
+		const int32_t c = at::scan_hits_bound(B.l1, max_dist);
+		run.ov_most = std::max(run.ov_most, (int)at::scan_overlap(B.l1, 1, c));
+		for (int64_t s0 = 0; s0 < bp; s0 += chunk) {
+			const int64_t n = std::min(chunk, bp - s0);
+			/* no pair has more candidates than its target has columns */
+			const long double mc = ((long double)(n / nt) + 2.0L) * (long double)tsum;   /* (the slice touches at most n / nt + 2 entries) */
+			const int64_t most_cand = mc > 4e18L ? (int64_t)4e18L : std::max<int64_t>(1, (int64_t)mc);
+			int64_t cap = std::min<int64_t>(cand_cap > 0 ? cand_cap : at::kScanHitsDefaultCand, most_cand);
+			at::ScanArgs sa;
+			memset(&sa, 0, sizeof sa);
+			sa.y0 = items_before(s0); sa.nitems = items_before(s0 + n) - sa.y0;
+			sa.s0 = s0; sa.npairs = n; sa.ntb = nt; sa.gall = gall; sa.gpre = d_gpre;
+			sa.qa = B.qa; sa.nq = (int)nq; sa.enc = enc; sa.nrev0 = (int)(nq + nt); sa.qperm = d_qperm;
+			sa.seq = rs.d_words; sa.swoff = (const long long *)rs.d_swoff; sa.slen = rs.d_len;
+			sa.tile = tile; sa.use_cutoff = 1; sa.cutoff = c;
+			const long long grid = std::max(1LL, std::min<long long>(sa.nitems, (long long)occ * h->ncu));
+			unsigned long long ncand = 0;
+			for (int turn = 0;; ++turn) {
+				rc = grow(h, &h->d_cand, &h->cand_bytes, cand_bytes(cap));
+				if (rc) return rc;
+				const Cand cd = cand_at(cap);
+				sa.cand_n = d_ncand; sa.cand_cap = cap; sa.cand_key = cd.k0; sa.cand_val = cd.v0;
+				HIP_TRY(h, hipMemsetAsync(d_ncand, 0, 8, s));
+				if (int rcq = ensure_queue(h, s)) return rcq;
+				sa.queue = h->d_queue;
+				HIP_TRY(h, hipEventRecord(ev.e[0], s));
+				HIP_TRY(h, at_scan_hits_launch(&sa, w, (unsigned)grid, s));
+				HIP_TRY(h, hipEventRecord(ev.e[1], s));
+				HIP_TRY(h, hipMemcpyAsync(&ncand, d_ncand, 8, hipMemcpyDeviceToHost, s));
+				HIP_TRY(h, hipStreamSynchronize(s));
+				float ms = 0.f;
+				HIP_TRY(h, hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+				run.sweep_ms += ms;
+				if (ncand <= (unsigned long long)cap) break;
+				/* they did not fit: the buffer goes, one of the counted size comes and the slice is swept once more (the count of a
+				 * slice does not depend on the order of its appends, so the second sweep fits) */
+				if (turn > 0 || ncand > (unsigned long long)most_cand)
+					return fail(h, AT_ERR_RANGE, "at_scan_hits: a slice counted %llu candidates after %lld", ncand, (long long)cap);
+				if (h->d_cand) { (void)hipFree(h->d_cand); h->d_cand = nullptr; h->cand_bytes = 0; }
+				cap = (int64_t)ncand;
+				++run.resweeps;
+			}
+			if (run.nslices == 0) {
+				char buf[200];
+				snprintf(buf, sizeof buf, "myers-scan-hits bits=2 words/lane=%d (1 read/wave, 64 tiles) lds=0B waves/cu<=%d grid=%lld", w, occ, grid);
+				run.cfg0 = buf;
+			}
+			++run.nslices;
+			run.cand += (long long)ncand;
+			if (ncand == 0) continue;
+			const Cand cd = cand_at(cap);
+			const long long nc = (long long)ncand;
+			size_t tmp_bytes = 0;
+			HIP_TRY(h, at_scanhits_sort(nullptr, &tmp_bytes, cd.k0, cd.k1, cd.v0, cd.v1, nc, n, s));
+			rc = grow(h, &h->d_sorttmp, &h->sorttmp_bytes, std::max<size_t>(tmp_bytes, 256));
+			if (rc) return rc;
+			HIP_TRY(h, at_scanhits_sort(h->d_sorttmp, &tmp_bytes, cd.k0, cd.k1, cd.v0, cd.v1, nc, n, s));
+			at::ScanHitsArgs ha;
+			memset(&ha, 0, sizeof ha);
+			ha.n = nc; ha.key = cd.k1; ha.val = cd.v1; ha.s0 = s0; ha.ntb = nt; ha.qa = B.qa; ha.enc = enc; ha.nrev0 = (int)(nq + nt);
+			ha.min_sep = min_sep; ha.qperm = d_qperm; ha.slen = rs.d_len; ha.flag = cd.flag; ha.off = cd.off; ha.hits = cd.hit; ha.qcount = d_qcount;
+			HIP_TRY(h, at_scanhits_mark_launch(&ha, h->ncu, s));
+			rc = scan_nops_device(h, nc, cd.flag, (int64_t *)cd.off, s);
+			if (rc) return rc;
+			HIP_TRY(h, at_scanhits_emit_launch(&ha, h->ncu, s));
+			HIP_TRY(h, hipEventRecord(ev.e[2], s));
+			long long kept = 0;
+			HIP_TRY(h, hipMemcpyAsync(&kept, cd.off + nc, 8, hipMemcpyDeviceToHost, s));
+			HIP_TRY(h, hipStreamSynchronize(s));
+			float ms = 0.f;
+			HIP_TRY(h, hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+			run.select_ms += ms;
+			if (kept < 0 || kept > nc) return fail(h, AT_ERR_RANGE, "at_scan_hits: %lld hits kept of %lld candidates", kept, nc);
+			if (kept > 0) {
+				const size_t was = hits.size();
+				hits.resize(was + (size_t)kept);
+				HIP_TRY(h, hipMemcpyAsync(hits.data() + was, cd.hit, (size_t)kept * sizeof(at::ScanHit), hipMemcpyDeviceToHost, s));
+				HIP_TRY(h, hipStreamSynchronize(s));
+			}
+			run.kept += kept;
+		}
+	}
+	qcount.assign((size_t)nq, 0);
+	if (nq > 0) {
+		HIP_TRY(h, hipMemcpyAsync(qcount.data(), d_qcount, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(h, hipStreamSynchronize(s));
+	}
+	at::scan_hits_order(hits.data(), (int64_t)hits.size());
+	return AT_OK;
+}
+
+extern "C" int at_scan_hits(at_handle *h,
+                            int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+                            int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+                            int32_t max_dist, int32_t min_sep, int strands, int32_t tile_cols, int64_t cand_cap, int flags,
+                            int64_t hit_cap, int64_t *out_hit_off,
+                            int32_t *out_target, int32_t *out_score, int32_t *out_end_j, int32_t *out_strand,
+                            int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_scan_hits: NULL handle");
+	if (nq < 0 || nt < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "at_scan_hits: negative size");
+	if (max_dist < 0) return fail(h, AT_ERR_ARG, "at_scan_hits: max_dist = %d is negative", max_dist);
+	if (min_sep < AT_SCAN_SEP_READ) return fail(h, AT_ERR_ARG, "at_scan_hits: min_sep = %d (a distance in columns, 0, or AT_SCAN_SEP_READ)", min_sep);
+	if (cand_cap < 0 || hit_cap < 0) return fail(h, AT_ERR_ARG, "at_scan_hits: negative capacity");
+	if (strands < AT_STRAND_FWD || strands > AT_STRAND_BOTH) return fail(h, AT_ERR_ARG, "at_scan_hits: strands = %d outside 1..3", strands);
+	if (tile_cols < 0 || (tile_cols & 15))
+		return fail(h, AT_ERR_ARG, "at_scan_hits: tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)", tile_cols, at::kScanDefaultTile);
+	if (flags & ~AT_CIGAR_M) return fail(h, AT_ERR_ARG, "at_scan_hits: flags = %d (AT_CIGAR_M or 0)", flags);
+	const bool rev = strands != AT_STRAND_FWD;
+	const bool cg = out_stats || out_ncigar || out_cigar_off || out_cigar;
+	if (cg && (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)))
+		return fail(h, AT_ERR_ARG, "at_scan_hits: the CIGAR outputs are either all NULL or all given");
+	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "at_scan_hits: %lld queries + %lld targets: at most 2^31 - 1 reads", (long long)nq, (long long)nt);
+	if (rev && (nt >= (1LL << 30) || 2 * nq + nt >= (1LL << 31)))
+		return fail(h, AT_ERR_ARG, "at_scan_hits: %lld queries, %lld targets: a reverse strand needs nt < 2^30 and 2 nq + nt < 2^31", (long long)nq, (long long)nt);
+	if (h->comm) return fail(h, AT_ERR_DOMAIN, "at_scan_hits: one GPU only (this handle belongs to a multi-process job)");
+	if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "at_scan_hits needs the unit mismatch cost: u = %d, not 1", h->u);
+	if (!out_hit_off) return fail(h, AT_ERR_ARG, "at_scan_hits: NULL argument");
+	if (nq > 0 && (!q_blob || !q_off || !q_len || (nt > 0 && (!t_blob || !t_off || !t_len))))
+		return fail(h, AT_ERR_ARG, "at_scan_hits: NULL argument");
+	if (hit_cap > 0 && (!out_target || !out_score || !out_end_j || (rev && !out_strand)))
+		return fail(h, AT_ERR_ARG, "at_scan_hits: NULL argument");
+	int32_t maxq = 0;
+	for (int64_t q = 0; q < nq; ++q) {
+		if (q_len[q] < 0 || q_off[q] < 0) return fail(h, AT_ERR_ARG, "query %lld: negative length or offset", (long long)q);
+		if (q_len[q] > at::kScanMaxQuery) return fail(h, AT_ERR_DOMAIN, "at_scan_hits: query %lld has %d bases, more than %d", (long long)q, q_len[q], at::kScanMaxQuery);
+		maxq = std::max(maxq, q_len[q]);
+	}
+	for (int64_t t = 0; t < nt; ++t)
+		if (t_len[t] < 0 || t_off[t] < 0) return fail(h, AT_ERR_ARG, "target %lld: negative length or offset", (long long)t);
+	const int32_t tile = tile_cols > 0 ? tile_cols : at::kScanDefaultTile;
+	return guarded(h, "at_scan_hits", [&]() -> int {
+		for (int64_t q = 0; q <= nq; ++q) out_hit_off[q] = 0;
+		ScanHitsRun run;
+		auto config = [&]() {
+			snprintf(h->cfg, sizeof h->cfg, "scan-hits: tile=%d overlap<=%d groups=%lld max_dist=%d min_sep=%d strands=%s, %lld blocks, %lld slices, "
+			         "candidates=%lld kept=%lld resweeps=%lld; %s sweep=%.3fms select=%.3fms", tile, run.ov_most, run.gall, max_dist, min_sep,
+			         scan_strands_text(strands), run.nblocks, run.nslices, run.cand, run.kept, run.resweeps, run.cfg0.c_str(), run.sweep_ms, run.select_ms);
+		};
+		if (nq == 0 || nt == 0) {
+			if (cg && hit_cap >= 0) out_cigar_off[0] = 0;
+			config();
+			return (int)AT_OK;
+		}
+		int64_t bytes = 0;
+		for (int64_t q = 0; q < nq; ++q) bytes += q_len[q];
+		for (int64_t t = 0; t < nt; ++t) bytes += t_len[t];
+		std::vector<uint8_t> blob((size_t)bytes + 32);
+		std::vector<int64_t> off((size_t)(nq + nt));
+		std::vector<int32_t> len((size_t)(nq + nt));
+		int64_t at = 0;
+		for (int64_t r = 0; r < nq + nt; ++r) {
+			const bool isq = r < nq;
+			const int32_t l = isq ? q_len[r] : t_len[r - nq];
+			if (l) memcpy(blob.data() + at, isq ? q_blob + q_off[r] : t_blob + t_off[r - nq], (size_t)l);
+			off[(size_t)r] = at; len[(size_t)r] = l; at += l;
+		}
+		ReadSet rs;
+		int rc = upload_reads(h, AT_MODE_EDIT, nq + nt, blob.data(), off.data(), len.data(), &rs, rev ? nq : 0);
+		if (rc) return rc;
+		if (rs.bits != 2) return fail(h, AT_ERR_DOMAIN, "at_scan_hits needs 2-bit reads: some base of a query or a target is not one of ACGT");
+		std::vector<at::ScanHit> hits;
+		std::vector<int32_t> qcount;
+		rc = scan_hits_lists(h, nq, q_len, nt, t_len, rs, max_dist, min_sep, strands, tile, cand_cap, hits, qcount, run);
+		if (rc) return rc;
+		config();
+		const int64_t nh = (int64_t)hits.size();
+		for (int64_t q = 0; q < nq; ++q) out_hit_off[q + 1] = out_hit_off[q] + qcount[(size_t)q];
+		if (out_hit_off[nq] != nh) return fail(h, AT_ERR_RANGE, "at_scan_hits: %lld hits fetched, %lld counted", (long long)nh, (long long)out_hit_off[nq]);
+		if (nh > hit_cap) return (int)AT_OK;               /* the caller comes back with room */
+		for (int64_t e = 0; e < nh; ++e) {
+			const at::ScanHit &x = hits[(size_t)e];
+			out_target[e] = x.target; out_score[e] = x.score; out_end_j[e] = x.end_j;
+			if (out_strand) out_strand[e] = x.strand;
+		}
+		if (!cg) return (int)AT_OK;
+		out_cigar_off[0] = 0;
+		if (nh == 0) return (int)AT_OK;
+		/* the window pass over the hits, in pieces that keep its descriptor and op buffers moderate */
+		const int64_t piece_hits = 1LL << 20, piece_ops = 1LL << 30;
+		auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+		std::vector<unsigned long long> lkey;
+		std::vector<int32_t> lej, leq, lei, p_ncigar, p_stats;
+		std::vector<int64_t> p_off;
+		std::string wcfg;
+		for (int64_t a = 0, b; a < nh; a = b) {
+			int64_t ops = 0;
+			for (b = a; b < nh && b - a < piece_hits; ++b) {
+				const at::ScanHit &x = hits[(size_t)b];
+				const int64_t one = 2LL * q_len[x.query] + x.score + 16;
+				if (b > a && ops + one > piece_ops) break;
+				ops += one;
+			}
+			const int64_t n = b - a;
+			lkey.assign((size_t)n, 0); lej.assign((size_t)n, 0); leq.assign((size_t)n, 0); lei.assign((size_t)n, 0);
+			for (int64_t e = 0; e < n; ++e) {
+				const at::ScanHit &x = hits[(size_t)(a + e)];
+				const uint32_t low = ~(uint32_t)(rev ? ((uint32_t)x.target << 1) | (uint32_t)x.strand : (uint32_t)x.target);
+				lkey[(size_t)e] = ((unsigned long long)((uint32_t)(-x.score) ^ 0x80000000u) << 32) | low;
+				lej[(size_t)e] = x.end_j; leq[(size_t)e] = x.query; lei[(size_t)e] = q_len[x.query];
+			}
+			const size_t bkey = al((size_t)n * 8), bl4 = al((size_t)n * 4);
+			rc = grow(h, &h->d_str, &h->str_bytes, bkey + 3 * bl4);
+			if (rc) return rc;
+			char *dl = (char *)h->d_str;
+			hipStream_t s = h->stream;
+			HIP_TRY(h, hipMemcpyAsync(dl, lkey.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+			HIP_TRY(h, hipMemcpyAsync(dl + bkey, leq.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(h, hipMemcpyAsync(dl + bkey + bl4, lej.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(h, hipStreamSynchronize(s));
+			const int64_t base = out_cigar_off[a];
+			const int64_t room = std::max<int64_t>(0, cigar_cap - base);
+			p_off.assign((size_t)n + 1, 0);
+			rc = scan_cigars(h, nq, 1, strands, rs, nt, maxq, bkey, bl4, out_target + a, out_score + a, lei.data(), out_end_j + a, flags,
+			                 out_stats + a * 8, out_ncigar + a, p_off.data(), room > 0 ? out_cigar + base : nullptr, room, n,
+			                 (const int *)(dl + bkey), "at_scan_hits");
+			if (rc) return rc;
+			for (int64_t e = 1; e <= n; ++e) out_cigar_off[a + e] = base + p_off[(size_t)e];
+			if (wcfg.empty()) { const char *w = strstr(h->cfg, "; windows: "); wcfg = w ? w : ""; }
+		}
+		config();
+		cfg_append(h, "%s", wcfg.c_str());
+		return (int)AT_OK;
 	});
 }
 

@@ -102,6 +102,10 @@ __global__ __launch_bounds__(64) void at_infix(const InfixArgs ea)
 				if (d < best) { best = d; best_j = t + 1; }
 			}
 		}
+		if constexpr (TB) {
+			/* end anchored (at_scan_hits' windows): the end cell is (l1, l2) with the value the fill ended on, whatever the minimum is */
+			if (ea.anchor_end && fits) { best = d; best_j = l2; }
+		}
 		if (have) {
 			if (fits) {
 				a.score[p] = best;

@@ -26,6 +26,9 @@
  * at_edit_tb's in PADDED row coordinates (row ip = pad + i; it stops at ip == pad): a column's value is 0 + the vertical differences
  * of the rows <= ip (the pad rows contribute 0, their words are skipped), and column 0 is ~pad (Pv = 1 on the real rows: D(i,0) = i).
  *
+ * anchor_end (TB, at_scan_hits' windows only): the walk starts in (l1, l2) with the value the fill ended on instead of (l1, j*) -- an
+ * occurrence that is not the best of its target is not the arg-min of its window either.
+ *
  * The word step is repeated here from at_myers.hip.h, as at_edit_tb.hip repeats it: the committed counter files fingerprint
  * at_myers.hip.h, so folding the three copies into one belongs to a change that re-collects the counters.
  */
@@ -40,6 +43,7 @@ struct InfixArgs {
 	const long long *ops_off;
 	uint32_t *slab;                /* TB: gridDim.x slabs of slab_words words */
 	long long slab_words;          /* max_l2 * W * 128 */
+	int anchor_end;                /* TB: the end cell is (l1, l2), not the arg-min of the last row (at_scan_hits; 0 everywhere else) */
 };
 
 }   // namespace at

@@ -24,7 +24,9 @@ AT_DEV uint32_t scan_or3(uint32_t a, uint32_t b, uint32_t c)
 /* the read entry e of qperm -> its read of the read set */
 AT_DEV int scan_query_read(int e, int enc, int nrev0) { return enc ? ((e & 1) ? nrev0 + (e >> 1) : e >> 1) : e; }
 
-template <int W>
+/* HITS: no best / best_j and no slot; the descents of the last row in own columns at or under the cutoff (which the host sets to
+ * c = min(max_dist, l1 - 1) per block) go to the slice's candidate buffer, one record per run of consecutive ones (at_scan.hip.h) */
+template <int W, bool HITS>
 __global__ __launch_bounds__(64) void at_scan(const ScanArgs a)
 {
 	constexpr bool PAD_S = W <= 16;                    /* 32 words: B0 / B1 take 64 SGPRs, the pad words stay in VGPRs */
@@ -75,6 +77,19 @@ __global__ __launch_bounds__(64) void at_scan(const ScanArgs a)
 		const int nwords_mine = (steps_mine + 15) >> 4;
 		uint32_t nxt = nwords_mine > 0 ? rw[0] : 0u;   /* the sixteen codes behind the ones in use */
 		int d = l1, best = l1, best_t = 0;             /* D(l1, s0 + t), its minimum so far and the first t that has it */
+		/* HITS: my own columns are s0 + t for own_lo < t <= steps_mine; the column in front of them is a warm-up column (or column 0) */
+		const int own_lo = HITS ? (int)(n * a.tile - s0) : 0;
+		const int hits_c = HITS ? scan_exact_bound(l1, a.use_cutoff, a.cutoff) : 0;
+		bool run_on = false;                           /* HITS: inside a run of descents; its first and its latest value */
+		int run_head = 0, run_tail = 0;
+		/* the record of a run that ends in column `col`: a slot from the counter, the store only while the slot exists */
+		auto append = [&](long long col, int tail, int head) {
+			const unsigned long long slot = atomicAdd(a.cand_n, 1ull);
+			if (slot < (unsigned long long)a.cand_cap) {
+				a.cand_key[slot] = scan_cand_key(p, col);
+				a.cand_val[slot] = scan_cand_val(tail, head);
+			}
+		};
 		for (int tw = 0; tw * 16 < nsteps; ++tw) {
 			uint32_t cw = nxt;
 			nxt = tw + 1 < nwords_mine ? rw[tw + 1] : 0u;
@@ -98,22 +113,39 @@ __global__ __launch_bounds__(64) void at_scan(const ScanArgs a)
 					Pv[w] = Mhs | ~(Xv | Phs);
 					Mv[w] = Phs & Xv;
 					pP = Ph; pM = Mh;
+					/* (HITS: left alone, the compiler sinks the Pv / Mv updates of all W words behind the candidate branch and keeps three
+					 * temporaries per word alive across it -- 120 VGPRs at 16 words, 248 at 32; pinned here they are made where they stand) */
+					if constexpr (HITS) asm volatile("" : "+v"(Pv[w]), "+v"(Mv[w]));
 				}
 				/* the last word's horizontal difference in its last row = D(l1, column) - D(l1, column - 1); behind my own tile the
 				 * lane steps on over whatever the word held and keeps what it had */
 				const int t1 = tw * 16 + cc + 1;
 				d += (int)(pP >> 31) - (int)(pM >> 31);
-				if (d < best && t1 <= steps_mine) { best = d; best_t = t1; }
+				if constexpr (HITS) {
+					/* a qualifying descent: own column, at or under c.  Consecutive ones are one RUN, and a run is one candidate record,
+					 * appended in the first column behind it (rarely true: the skipped block holds the atomic and the stores) */
+					const bool q = (pM >> 31) && d <= hits_c && t1 > own_lo && t1 <= steps_mine;
+					if (run_on && !q) append(s0 + t1 - 1, run_tail, run_head);
+					run_head = q && !run_on ? d : run_head;
+					run_tail = q ? d : run_tail;
+					run_on = q;
+				} else {
+					if (d < best && t1 <= steps_mine) { best = d; best_t = t1; }
+				}
 			}
 		}
-		/* ---- the group's minimum of (score, absolute column), folded into the pair's slot ---- */
-		unsigned long long key = steps_mine > 0 ? ((unsigned long long)(unsigned)best << 32) | (unsigned long long)(s0 + best_t) : ~0ull;
+		if constexpr (HITS) {
+			if (run_on) append(s0 + steps_mine, run_tail, run_head);   /* (a run up to my last column, which was the wave's last step) */
+		} else {
+			/* ---- the group's minimum of (score, absolute column), folded into the pair's slot ---- */
+			unsigned long long key = steps_mine > 0 ? ((unsigned long long)(unsigned)best << 32) | (unsigned long long)(s0 + best_t) : ~0ull;
 #pragma unroll
-		for (int x = 32; x >= 1; x >>= 1) {
-			const unsigned long long o = __shfl_xor(key, x, 64);
-			key = o < key ? o : key;
+			for (int x = 32; x >= 1; x >>= 1) {
+				const unsigned long long o = __shfl_xor(key, x, 64);
+				key = o < key ? o : key;
+			}
+			if (lane == 0 && key != ~0ull) atomicMin(a.key + p, key);
 		}
-		if (lane == 0 && key != ~0ull) atomicMin(a.key + p, key);
 	}
 }
 
@@ -160,7 +192,7 @@ __global__ __launch_bounds__(256) void at_scan_window_k(const ScanWindowArgs a)
 			a.woff1[e] = 0; a.woff2[e] = 0; a.len1[e] = 0; a.len2[e] = 0; a.ws[e] = 0;   /* an empty pair: no ops, no runs */
 			continue;
 		}
-		const int q = (int)(e / a.k), qr = strand ? a.nrev0 + q : q, l1 = a.slen[qr], ej = a.lej[e];
+		const int q = a.eq ? a.eq[e] : (int)(e / a.k), qr = strand ? a.nrev0 + q : q, l1 = a.slen[qr], ej = a.lej[e];
 		const int ws = (int)scan_window_start(ej, l1, score);
 		a.woff1[e] = a.swoff[qr]; a.len1[e] = l1;
 		a.woff2[e] = a.swoff[a.nq + target] + (ws >> 4); a.len2[e] = ej - ws;
@@ -187,19 +219,31 @@ __global__ __launch_bounds__(256) void at_scan_check_k(const ScanWindowArgs a)
 
 }   // namespace at
 
-extern "C" const void *at_scan_kernel(int w)
+template <bool HITS>
+static const void *scan_kernel_of(int w)
 {
-	return w == 2 ? (const void *)at::at_scan<2> : w == 3 ? (const void *)at::at_scan<3> : w == 4 ? (const void *)at::at_scan<4>
-	     : w == 5 ? (const void *)at::at_scan<5> : w == 8 ? (const void *)at::at_scan<8> : w == 16 ? (const void *)at::at_scan<16>
-	     : w == 32 ? (const void *)at::at_scan<32> : nullptr;
+	return w == 2 ? (const void *)at::at_scan<2, HITS> : w == 3 ? (const void *)at::at_scan<3, HITS> : w == 4 ? (const void *)at::at_scan<4, HITS>
+	     : w == 5 ? (const void *)at::at_scan<5, HITS> : w == 8 ? (const void *)at::at_scan<8, HITS> : w == 16 ? (const void *)at::at_scan<16, HITS>
+	     : w == 32 ? (const void *)at::at_scan<32, HITS> : nullptr;
 }
 
-extern "C" hipError_t at_scan_launch(const at::ScanArgs *a, int w, unsigned grid, hipStream_t s)
+extern "C" const void *at_scan_kernel(int w) { return scan_kernel_of<false>(w); }
+extern "C" const void *at_scan_hits_kernel(int w) { return scan_kernel_of<true>(w); }
+
+static hipError_t scan_launch_fn(const void *k, const at::ScanArgs *a, unsigned grid, hipStream_t s)
 {
-	void (*fn)(const at::ScanArgs) = (void (*)(const at::ScanArgs))at_scan_kernel(w);
+	void (*fn)(const at::ScanArgs) = (void (*)(const at::ScanArgs))k;
 	if (!fn) return hipErrorInvalidValue;
 	hipLaunchKernelGGL(fn, dim3(grid), dim3(64), 0, s, *a);
 	return hipGetLastError();
+}
+
+extern "C" hipError_t at_scan_launch(const at::ScanArgs *a, int w, unsigned grid, hipStream_t s) { return scan_launch_fn(at_scan_kernel(w), a, grid, s); }
+
+extern "C" hipError_t at_scan_hits_launch(const at::ScanArgs *a, int w, unsigned grid, hipStream_t s)
+{
+	if (!a->cand_n || a->cand_cap < 0 || (a->cand_cap > 0 && (!a->cand_key || !a->cand_val))) return hipErrorInvalidValue;
+	return scan_launch_fn(at_scan_hits_kernel(w), a, grid, s);
 }
 
 static unsigned scan_small_grid(long long n, int ncu) { return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8LL * ncu)); }

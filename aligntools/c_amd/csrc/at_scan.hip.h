@@ -27,10 +27,19 @@
  *   (at_infix<W, true> and the CIGAR kernels, unchanged)
  *   at_scan_check_k    the window's score and end column must reproduce the hit (a flag word otherwise); AT_CG_START_J += ws;
  *                      unused entries: 0 runs and a statistics row of -1
+ *
+ * at_scan<W, true> (at_scan_hits) is the same sweep without best / best_j, shuffles and slot: per column a lane asks
+ * whether the sign pair says -1, d <= c and the column is an OWN column (warm-up columns never count here: a tile sees exactly the
+ * descents of its own columns), keeps the run of such descents in consecutive columns (first value, latest value) and, in the first
+ * column behind a run, appends ONE record to the slice's candidate buffer: an atomicAdd on the slice's counter, which counts on past
+ * the capacity, and the stores only while the index is below it.  The block with the atomic and the stores is skipped by the wave
+ * when no lane has a record.  Behind the sweep: sort, marking, compaction (at_scanhits.hip.h); the window kernels serve the kept hits
+ * with the query of each entry in `eq` and END-ANCHORED windows (InfixArgs::anchor_end).
  */
 #pragma once
 #include "at_myers.hip.h"
 #include "at_scanplan.h"
+#include "at_scanhits.h"
 
 namespace at {
 
@@ -49,6 +58,13 @@ struct ScanArgs {
 	unsigned long long *key;       /* [npairs] */
 	unsigned long long *queue;
 	int *score, *end_i, *end_j, *state;   /* at_scan_unpack_k: [npairs] */
+	/* at_scan<W, true>: the slice's candidate records (at_scanhits.h), key = (pair of the slice << 32) | last column of a run of
+	 * descents, val = its last and first value; *cand_n counts every record, stored or not: one is stored only while its index is
+	 * below cand_cap */
+	unsigned long long *cand_n;
+	long long cand_cap;
+	unsigned long long *cand_key;
+	int *cand_val;
 };
 
 struct ScanWindowArgs {
@@ -56,6 +72,7 @@ struct ScanWindowArgs {
 	int k, nq, enc, nrev0;
 	const unsigned long long *lkey;   /* the lists of at_search_merge_k */
 	const int *lej;
+	const int *eq;                 /* the query of entry e, or NULL: e / k */
 	const long long *swoff;
 	const int *slen;
 	long long *woff1, *woff2;      /* out: the window pairs */
@@ -74,6 +91,8 @@ struct ScanWindowArgs {
 extern "C" const void *at_scan_kernel(int w);
 extern "C" hipError_t at_scan_init_launch(const at::ScanArgs *a, int ncu, hipStream_t s);
 extern "C" hipError_t at_scan_launch(const at::ScanArgs *a, int w, unsigned grid, hipStream_t s);
+extern "C" const void *at_scan_hits_kernel(int w);
+extern "C" hipError_t at_scan_hits_launch(const at::ScanArgs *a, int w, unsigned grid, hipStream_t s);
 extern "C" hipError_t at_scan_unpack_launch(const at::ScanArgs *a, int ncu, hipStream_t s);
 extern "C" hipError_t at_scan_window_launch(const at::ScanWindowArgs *a, int ncu, hipStream_t s);
 extern "C" hipError_t at_scan_check_launch(const at::ScanWindowArgs *a, int ncu, hipStream_t s);

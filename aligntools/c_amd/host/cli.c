@@ -156,6 +156,11 @@ static int main_single(int cmd, int argc, char *argv[])
  *     --scan         (edit -u 1 --infix --queries, with --score-only or --paf) reads against LONG targets (at_scan): the hits of the
  *                    --queries form with no bound on the target length; --score-only prints their hit lines, --paf their PAF lines
  *                    (target start and end absolute, cg:Z the =/X CIGAR).  Not with --all-vs-all, --gpus N > 1.
+ *     --all-hits D   (with --scan) EVERY occurrence of every read with at most D edits (at_scan_hits) instead of the best K hits:
+ *                    --score-only prints "query\ttarget\tedit_distance=d\tend=J" per hit (J the absolute end column; "\t+" / "\t-"
+ *                    with --both-strands), --paf the PAF line of --scan.  --min-sep S keeps an occurrence only if no better one
+ *                    of the same read, strand and target lies within S columns (0: all; default -1: the read's own length).
+ *                    Not with --best; D >= 0.
  *     --gpus N       one process per GPU: this process starts N workers (itself, with AT_RANK / AT_WORLD / AT_DEVICE /
  *                    AT_COMM_DIR in their environment), rank 0's options are broadcast over RCCL, every rank aligns a
  *                    contiguous share of the pairs on its own GPU, results are gathered over RCCL and rank 0 prints them
@@ -164,7 +169,7 @@ static int main_single(int cmd, int argc, char *argv[])
  * thread -- which also pays the HIP start-up, in the shadow of the first chunks' parsing -- sends each chunk to the GPU
  * and writes its results with one fwrite.  Memory is bounded by the chunks in flight, whatever the size of the file;
  * --all-vs-all keeps the read set and streams slices of the triangle instead (at_align_allpairs_stream). */
-typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments, infix, scan; } batch_flags;
+typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments, infix, scan; int all_hits, max_dist, sep_set, min_sep; } batch_flags;
 static int g_edit_alignments;   /* --alignments: every handle of this process delivers edit alignments (set before any handle exists) */
 static int g_edit_infix;        /* --infix: every handle of this process is in edit infix mode (at_set_edit_infix; set likewise) */
 
@@ -835,6 +840,79 @@ static int batch_scan(opt_t *opt, const batch_flags *bf, const char *qfile, cons
 	return 0;
 }
 
+/* ---- --scan --all-hits D [--min-sep S]: every occurrence of every read with at most D edits (at_scan_hits) ----
+ * --score-only prints "query\ttarget\tedit_distance=d\tend=J" (and "\t+" / "\t-" with --both-strands) per hit, --paf the scan's PAF line */
+static int batch_scan_hits(opt_t *opt, const batch_flags *bf, const char *qfile, const char *tfile)
+{
+	at_reader *rq = at_reader_open(qfile), *rt;
+	at_chunk c;
+	at_handle *h;
+	tbuf out = {NULL, 0, 0};
+	int64_t nq, nt, q, x, e, *qoff, *toff, *hoff, *cgoff = NULL, cap = 0, hcap;
+	int32_t *qlen, *tlen, *tgt = NULL, *sc = NULL, *ej = NULL, *sd = NULL, *stats = NULL, *ncg = NULL;
+	uint32_t *cg = NULL;
+	int rc, pass;
+	if (!rq) die("Can't open %s\n", qfile);
+	rt = at_reader_open(tfile);
+	if (!rt) die("Can't open %s\n", tfile);
+	memset(&c, 0, sizeof c);
+	while (at_reader_read(rq, (size_t)-1, (size_t)-1, &c) > 0) {}
+	nq = (int64_t)c.n;
+	while (at_reader_read(rt, (size_t)-1, (size_t)-1, &c) > 0) {}
+	nt = (int64_t)c.n - nq;
+	at_reader_close(rq); at_reader_close(rt);
+	if (nq == 0 || nt == 0) { at_chunk_free(&c); return 0; }
+	h = at_host_handle();
+	rc = at_set_scoring(h, opt->m, opt->u, opt->o, opt->e, opt->j, 0, NULL, 0);
+	if (rc != AT_OK) die("%s", at_last_error(h));
+	qoff = (int64_t *)at_xmalloc((size_t)nq * 8); qlen = (int32_t *)at_xmalloc((size_t)nq * 4);
+	toff = (int64_t *)at_xmalloc((size_t)nt * 8); tlen = (int32_t *)at_xmalloc((size_t)nt * 4);
+	hoff = (int64_t *)at_xmalloc((size_t)(nq + 1) * 8);
+	for (q = 0; q < nq; ++q) { qoff[q] = (int64_t)c.off[q]; qlen[q] = (int32_t)c.len[q]; }
+	for (x = 0; x < nt; ++x) { toff[x] = (int64_t)c.off[nq + x]; tlen[x] = (int32_t)c.len[nq + x]; }
+	hcap = 4 * nq + 64;
+	trace("scan-hits: records read, queries", nq);
+	for (pass = 0; pass < 3; ++pass) {       /* again with room if there are more hits, or more runs, than the guess before */
+		free(tgt); free(sc); free(ej); free(sd); free(stats); free(ncg); free(cgoff); free(cg);
+		stats = NULL; ncg = NULL; cgoff = NULL; cg = NULL;
+		tgt = (int32_t *)at_xmalloc((size_t)hcap * 4 + 4); sc = (int32_t *)at_xmalloc((size_t)hcap * 4 + 4);
+		ej = (int32_t *)at_xmalloc((size_t)hcap * 4 + 4); sd = (int32_t *)at_xmalloc((size_t)hcap * 4 + 4);
+		if (bf->paf) {
+			stats = (int32_t *)at_xmalloc((size_t)hcap * 32 + 32); ncg = (int32_t *)at_xmalloc((size_t)hcap * 4 + 4);
+			cgoff = (int64_t *)at_xmalloc((size_t)(hcap + 1) * 8);
+			if (cap < 16 * hcap + 64) cap = 16 * hcap + 64;
+			cg = (uint32_t *)at_xmalloc((size_t)cap * 4);
+		}
+		rc = at_scan_hits(h, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, bf->max_dist, bf->min_sep, bf->both ? AT_STRAND_BOTH : AT_STRAND_FWD,
+		                  0, 0, 0, hcap, hoff, tgt, sc, ej, sd, stats, ncg, cgoff, cg, cap);
+		if (rc != AT_OK) die("%s", at_last_error(h));
+		if (hoff[nq] > hcap) { hcap = hoff[nq]; continue; }
+		if (!bf->paf || cgoff[hoff[nq]] <= cap) break;
+		cap = cgoff[hoff[nq]];
+	}
+	trace("scan-hits: done, hits", hoff[nq]);
+	for (q = 0; q < nq; ++q) {
+		for (e = hoff[q]; e < hoff[q + 1]; ++e) {
+			const char strand = sd[e] == 1 ? '-' : '+';
+			const char *qn = c.names + c.name_off[q], *tn = c.names + c.name_off[nq + tgt[e]];
+			if (bf->paf)
+				tb_paf(&out, qn, qlen[q], strand, tn, tlen[tgt[e]], -sc[e], qlen[q], ej[e], stats + 8 * e, cg + cgoff[e], ncg[e]);
+			else {
+				tb_need(&out, strlen(qn) + strlen(tn) + 96);
+				out.l += (size_t)sprintf(out.s + out.l, "%s\t%s\tedit_distance=%d\tend=%d", qn, tn, (int)sc[e], (int)ej[e]);
+				if (bf->both) { out.s[out.l++] = '\t'; out.s[out.l++] = strand; }
+				out.s[out.l++] = '\n';
+			}
+		}
+		if (out.l > ((size_t)8 << 20)) tb_flush(&out);
+	}
+	tb_flush(&out);
+	free(out.s); free(qoff); free(qlen); free(toff); free(tlen); free(hoff); free(tgt); free(sc); free(ej); free(sd);
+	free(stats); free(ncg); free(cgoff); free(cg);
+	at_chunk_free(&c);
+	return 0;
+}
+
 /* start one worker per GPU (this binary again, told its rank through the environment) and wait for them */
 static int batch_launch(int world, char *argv0, int argc, char *argv[])
 {
@@ -894,10 +972,10 @@ static int main_batch(int argc, char *argv[], char *argv0)
 {
 	int cmd = -1, k, n = 0;
 	opt_t *opt = init_opt();
-	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0, 0, 0};
+	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, AT_SCAN_SEP_READ};
 	char **av = (char **)at_xmalloc((size_t)(argc + 1) * sizeof(char *));
 	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] [--paf] [--alignments] [--infix] [--scan] <pairs.fa>\n"
-	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] [--infix] [--scan] <targets.fa>\n";
+	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] [--infix] [--scan] [--all-hits D] [--min-sep S] <targets.fa>\n";
 	/* the long flags of the extension are taken out before getopt sees the reference's short options */
 	for (k = 0; k < argc; ++k) {
 		if (strcmp(argv[k], "--score-only") == 0) bf.score_only = 1;
@@ -911,6 +989,8 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (strcmp(argv[k], "--alignments") == 0) bf.alignments = 1;
 		else if (strcmp(argv[k], "--infix") == 0) bf.infix = 1;
 		else if (strcmp(argv[k], "--scan") == 0) bf.scan = 1;
+		else if (strcmp(argv[k], "--all-hits") == 0 && k + 1 < argc) { bf.all_hits = 1; bf.max_dist = atoi(argv[++k]); }
+		else if (strcmp(argv[k], "--min-sep") == 0 && k + 1 < argc) { bf.sep_set = 1; bf.min_sep = atoi(argv[++k]); }
 		else av[n++] = argv[k];
 	}
 	av[n] = NULL;
@@ -920,7 +1000,12 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	/* --queries: refused with what it cannot go with, before any GPU call */
 	{
 		const char *why = NULL;
-		if (bf.scan && !bf.infix) why = "--scan goes with edit -u 1 --infix";
+		if (bf.all_hits && !bf.scan) why = "--all-hits goes with --scan";
+		else if (bf.all_hits && bf.best_set) why = "--all-hits does not go with --best (it reports every occurrence)";
+		else if (bf.sep_set && !bf.all_hits) why = "--min-sep goes with --all-hits";
+		else if (bf.all_hits && bf.max_dist < 0) why = "--all-hits D needs D >= 0";
+		else if (bf.sep_set && bf.min_sep < AT_SCAN_SEP_READ) why = "--min-sep S needs S >= 0 (or -1: each read's own length)";
+		else if (bf.scan && !bf.infix) why = "--scan goes with edit -u 1 --infix";
 		else if (bf.scan && bf.all_vs_all) why = "--scan does not go with --all-vs-all";
 		else if (bf.scan && !bf.queries) why = "--scan goes with --queries (reads against long targets)";
 		else if (bf.scan && bf.gpus > 1) why = "--scan runs on one GPU: it does not go with --gpus N > 1";
@@ -954,7 +1039,8 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	g_edit_alignments = bf.alignments;
 	g_edit_infix = bf.infix;
 	if (bf.queries) {
-		k = bf.scan ? batch_scan(opt, &bf, bf.queries, av[n - 1]) : batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
+		k = bf.all_hits ? batch_scan_hits(opt, &bf, bf.queries, av[n - 1])
+		  : bf.scan ? batch_scan(opt, &bf, bf.queries, av[n - 1]) : batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
 		free(opt->sites.pos); free(opt); free(av);
 		return k;
 	}

@@ -423,6 +423,46 @@ int at_scan_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutoff, int
                  int32_t *tile, int32_t *overlap, int64_t *ngroups);
 
 /*
+ * EVERY occurrence of a read under a distance cutoff: at_scan keeps one hit per (query, strand, target); this entry
+ * reports every one.  For a query of l1 >= 1 bases, a target of l2 bases and max_dist >= 0 let c = min(max_dist, l1 - 1) (a match
+ * must cost less than deleting the whole read; a query of length 0 has no hits) and D the table of at_scan, D(0,j) = 0, D(i,0) = i.
+ *   occurrence  column a >= 1 with v = D(l1,a) is an OCCURRENCE iff v <= c, D(l1,a-1) > v and, with b the last column of the run of
+ *               columns a..b that all hold v, b == l2 or D(l1,b+1) > v: the leftmost column of each strict local minimum of the last
+ *               row, plateaus included (the "first column wins" choice of at_scan and of the local arg-max)
+ *   separation  with min_sep = s > 0 an occurrence (a, v) of a (query, strand, target) is reported iff no OTHER OCCURRENCE (a', v') of
+ *               the same triple with |a - a'| <= s has (v', a') < (v, a) lexicographically.  s = 0 reports every occurrence;
+ *               s = AT_SCAN_SEP_READ (-1) stands for each query's own length.  A window minimum, not a greedy chain: a hit may be
+ *               dropped by a neighbour that is itself dropped, which makes the result independent of any processing order
+ *   hit         target, strand (0 = the query as given, 1 = its reverse complement), distance v, end cell (l1, a) with a the
+ *               ABSOLUTE column, state AT_ST_MID.  Its ops are those of at_scan's three-way rule walked on the full table from
+ *               (l1, a); AT_CG_START_J is absolute
+ *   order       the hits of a query by distance, then target index, then strand 0 first, then column (at_scan's rank, extended)
+ * out_hit_off (nq + 1 entries) is ALWAYS complete: the hits of query q are the entries [out_hit_off[q], out_hit_off[q + 1]).  If
+ * out_hit_off[nq] > hit_cap nothing else is written and the call returns AT_OK: the caller calls again with room.  Otherwise
+ * out_target / out_score / out_end_j / out_strand (hit_cap entries each; out_strand may be NULL for AT_STRAND_FWD) hold the hits,
+ * and the four CIGAR outputs, all NULL or all given, are laid out over the hits as in at_align_batch_cigar (out_stats 8 per hit,
+ * out_cigar_off out_hit_off[nq] + 1 entries, words of the hits that end within cigar_cap; flags: AT_CIGAR_M or 0).
+ *   tile_cols   as at_scan; the results do not depend on it
+ *   cand_cap    the candidate records (12 bytes each, descents of the last row at or under c) a slice of pairs may leave on the
+ *               device; 0 = the library's default (2^20, or the columns of the slice if that is less).  A slice with more is swept
+ *               once more into a buffer of the counted size: the results do not depend on it.  AT_ERR_NOMEM only if that
+ *               allocation fails
+ * Queries of up to 1 024 bases, pure ACGT, u == 1; one GPU; synchronous.  The handle's at_set_edit_infix / at_set_edit_traceback
+ * settings neither matter nor change.  AT_ERR_DOMAIN as at_scan; AT_ERR_ARG as at_scan and for max_dist < 0, min_sep < -1,
+ * cand_cap < 0, hit_cap < 0.  at_last_config: "scan-hits: tile=T overlap<=OV groups=G max_dist=D min_sep=S strands=fwd|rev|both,
+ * B blocks, S slices, candidates=N kept=M resweeps=R; myers-scan-hits bits=2 words/lane=W ..." and, with CIGARs, "; windows: " and
+ * the window pass's text.
+ */
+#define AT_SCAN_SEP_READ (-1)
+int at_scan_hits(at_handle *h,
+                 int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+                 int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+                 int32_t max_dist, int32_t min_sep, int strands, int32_t tile_cols, int64_t cand_cap, int flags,
+                 int64_t hit_cap, int64_t *out_hit_off,
+                 int32_t *out_target, int32_t *out_score, int32_t *out_end_j, int32_t *out_strand,
+                 int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap);
+
+/*
  * Multi-process batches: one process per GPU, each with its own handle.  The pairs are independent, so
  * the only communication is a broadcast of rank 0's scoring block and a gather of results, both RCCL collectives on the
  * handles' devices (over xGMI inside a node).  `dir` is a directory all ranks can reach: rank 0 leaves the RCCL id there.
