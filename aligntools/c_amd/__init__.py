@@ -32,7 +32,7 @@ SCAN_SEP_READ = -1              # AT_SCAN_SEP_READ: min_sep of Aligner.scan_hits
 ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_set_edit_traceback", "at_set_edit_infix", "at_align_batch",
                "at_align_batch_device", "at_align_allpairs_device", "at_render_batch_device", "at_compact_ops_device",
                "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream", "at_search",
-               "at_search_strands", "at_scan", "at_scan_plan", "at_scan_hits", "at_revcomp", "at_revcomp_device",
+               "at_search_strands", "at_scan", "at_scan_plan", "at_scan_hits", "at_allpairs_hits", "at_revcomp", "at_revcomp_device",
                "at_cigar", "at_cigar_batch_device", "at_align_batch_cigar",
                "at_comm_init", "at_comm_broadcast_scoring", "at_comm_allgather", "at_comm_destroy", "at_comm_abi_checked",
                "at_pack_words", "at_pack_batch", "at_render", "at_last_config"]
@@ -139,6 +139,9 @@ def load_library():
     lib.at_scan_hits.restype = C.c_int
     lib.at_scan_hits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int64, C.c_int, C.c_int64] + [C.c_void_p] * 9 + [C.c_int64]
+    lib.at_allpairs_hits.restype = C.c_int
+    lib.at_allpairs_hits.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
+                                     C.c_int, C.c_int64] + [C.c_void_p] * 12 + [C.c_int64]
     lib.at_scan_plan.restype = C.c_int
     lib.at_scan_plan.argtypes = [C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int32, _i32p, _i32p, _i64p]
     lib.at_revcomp.restype = C.c_int
@@ -625,6 +628,55 @@ class Aligner:
         if cigar:
             res["stats"], res["ncigar"], res["cigar_off"] = stats[:n].copy(), ncigar[:n].copy(), cigar_off[:n + 1].copy()
             res["cigar"] = [words[cigar_off[e]:cigar_off[e] + max(int(ncigar[e]), 0)].copy() for e in range(n)]
+        return res
+
+    def allpairs_hits(self, mode, reads, threshold, first_pair=0, npairs=None, cigar=False, cigar_m=False, chunk_pairs=0):
+        """All-vs-all over `reads` (a list of str or bytes) of which only the pairs over a threshold come back (at_allpairs_hits): the
+        pairs (a < b) of the triangle's range [first_pair, first_pair + npairs) -- npairs None: to its end -- whose score is >=
+        threshold (edit: whose distance is <= threshold), in ascending pair order.  Returns a dict: pair (int64, the triangle index)
+        and a, b, score, end_i, end_j, state (int32) over the hits, exactly what align_allpairs_stream gives for those pairs; with
+        cigar=True (not for edit) also stats (nhits, 8), ncigar (nhits,), cigar_off (nhits + 1,) and cigar, a list of numpy uint32
+        arrays ('=' / 'X'; cigar_m: 'M').  With "overlap" the pairs the bit-parallel bound proves below the threshold are not swept;
+        the handle's set_min_score setting is the same afterwards.  chunk_pairs (pairs per slice; 0: the default) does not change
+        the results."""
+        if isinstance(mode, str):
+            mode = MODES[mode]
+        rs = [_b(x) for x in reads]
+        n = len(rs)
+        lens = np.fromiter((len(x) for x in rs), dtype=np.int32, count=n)
+        off = np.zeros(n, dtype=np.int64)
+        if n > 1:
+            np.cumsum(lens[:-1], out=off[1:])
+        blob = np.frombuffer(b"".join(rs) + b"\0", dtype=np.uint8).copy()
+        if npairs is None:
+            npairs = n * (n - 1) // 2 - int(first_pair)
+        nhits = C.c_int64(0)
+        hit_cap, cap = 4 * n + 1024, 0
+        for _ in range(3):                                      # more hits, then more runs, than the first guess has room for
+            pair = np.zeros(hit_cap, dtype=np.int64)
+            out = {name: np.zeros(hit_cap, dtype=np.int32) for name in ("a", "b", "score", "end_i", "end_j", "state")}
+            stats = np.full((hit_cap, 8), -1, dtype=np.int32) if cigar else None
+            ncigar = np.zeros(hit_cap, dtype=np.int32) if cigar else None
+            cigar_off = np.zeros(hit_cap + 1, dtype=np.int64) if cigar else None
+            cap = max(cap, 16 * hit_cap + 64)
+            words = np.zeros(cap, dtype=np.uint32) if cigar else None
+            self._check(self._lib.at_allpairs_hits(self._h, mode, n, _ptr(blob), _ptr(off), _ptr(lens), int(first_pair), int(npairs),
+                                                   int(threshold), int(chunk_pairs), CIGAR_M if cigar_m else 0, hit_cap, C.addressof(nhits),
+                                                   _ptr(pair), _ptr(out["a"]), _ptr(out["b"]), _ptr(out["score"]), _ptr(out["end_i"]),
+                                                   _ptr(out["end_j"]), _ptr(out["state"]), _ptr(stats), _ptr(ncigar), _ptr(cigar_off),
+                                                   _ptr(words), cap if cigar else 0))
+            k = int(nhits.value)
+            if k > hit_cap:
+                hit_cap = k
+                continue
+            if not cigar or cigar_off[k] <= cap:
+                break
+            cap = int(cigar_off[k])
+        res = {name: a[:k].copy() for name, a in out.items()}
+        res["pair"] = pair[:k].copy()
+        if cigar:
+            res["stats"], res["ncigar"], res["cigar_off"] = stats[:k].copy(), ncigar[:k].copy(), cigar_off[:k + 1].copy()
+            res["cigar"] = [words[cigar_off[e]:cigar_off[e] + max(int(ncigar[e]), 0)].copy() for e in range(k)]
         return res
 
     def align_allpairs_device(self, mode, nreads, d_seq, bits, d_woff, d_len, max_len, first_pair, npairs, want_traceback,

@@ -17,6 +17,7 @@
 #include "at_infix.hip.h"
 #include "at_scan.hip.h"
 #include "at_scanhits.hip.h"
+#include "at_pairhits.hip.h"
 #include "../../../include/aligntools_hip.h"
 
 #include <algorithm>
@@ -3198,6 +3199,242 @@ extern "C" int at_align_allpairs(at_handle *h, int mode, int64_t nreads, const u
 			                        out_end_j ? out_end_j + lo : nullptr, out_state ? out_state + lo : nullptr, out_ops, ops_off + lo, out_nops + lo);
 			if (rc2) return rc2;
 		}
+		return (int)AT_OK;
+	});
+}
+
+/* ---- all-vs-all of which only the pairs over a threshold leave the device (at_allpairs_hits; the stages: at_pairhits.hip.h) ----
+ * The slices, their two buffer sets and their events are those of allpairs_scores; what differs is behind the sweep: the flag, prefix
+ * sum and emit kernels on the handle's stream, then 16 bytes (the smallest pair outside the domain, the kept count) on the copy
+ * stream, and -- once the host has the count, while the next slice is swept -- the kept records. */
+struct PairHitsRun { int64_t nslices = 0, chunk = 0; std::string cfg0; };
+
+static int allpairs_hit_slices(at_handle *h, int mode, int64_t nreads, const ReadSet &rs, int64_t first_pair, int64_t npairs,
+                               int64_t chunk, int32_t threshold, std::vector<at::PairHit> &hits, PairHitsRun &run)
+{
+	if (chunk <= 0) chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
+	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(npairs, 1LL << 28)));
+	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	const size_t b_res = al((size_t)chunk * 4), b_off = al((size_t)(chunk + 1) * 8), b_rec = al((size_t)chunk * sizeof(at::PairHit));
+	int rc = grow(h, &h->d_out, &h->out_bytes, 2 * 4 * b_res);
+	if (rc) return rc;
+	/* [flags | prefix sums | 2 x (the two 64-bit slots | the slice's records)] */
+	rc = grow(h, &h->d_cand, &h->cand_bytes, b_res + b_off + 2 * (256 + b_rec));
+	if (rc) return rc;
+	if (h->pin_bytes < 256) {
+		if (h->h_pin) { (void)hipHostFree(h->h_pin); h->h_pin = nullptr; h->pin_bytes = 0; }
+		if (hipHostMalloc(&h->h_pin, 4096, hipHostMallocDefault) != hipSuccess) {
+			h->h_pin = nullptr;
+			(void)hipGetLastError();   /* (as in grow) */
+			return fail(h, AT_ERR_NOMEM, "hipHostMalloc(%d) for the slices' counts failed", 4096);
+		}
+		h->pin_bytes = 4096;
+	}
+	if (!h->copy_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+	for (int q = 0; q < 2; ++q) {
+		if (!h->ev_sweep[q]) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_sweep[q], hipEventDisableTiming));
+		if (!h->ev_copy[q]) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_copy[q], hipEventDisableTiming));
+	}
+	hipStream_t s = h->stream, cs = h->copy_stream;
+	const int64_t nchunks = (npairs + chunk - 1) / chunk;
+	char *dsel = (char *)h->d_cand;
+	int *d_flag = (int *)dsel;
+	long long *d_off = (long long *)(dsel + b_res);
+	auto dres = [&](int q, int a) { return (int32_t *)((char *)h->d_out + ((size_t)q * 4 + (size_t)a) * b_res); };
+	auto dslots = [&](int q) { return (unsigned long long *)(dsel + b_res + b_off + (size_t)q * (256 + b_rec)); };
+	auto drec = [&](int q) { return (at::PairHit *)(dsel + b_res + b_off + (size_t)q * (256 + b_rec) + 256); };
+	auto hslots = [&](int q) { return (volatile unsigned long long *)((char *)h->h_pin + (size_t)q * 64); };
+	auto deliver = [&](int64_t c) -> int {
+		const int q = (int)(c & 1);
+		const int64_t lo = c * chunk, n = std::min(chunk, npairs - lo);
+		HIP_TRY(h, hipEventSynchronize(h->ev_copy[q]));
+		const unsigned long long bad = hslots(q)[0], kept = hslots(q)[1];
+		if (bad != at::kPairHitsNoBad)
+			return fail(h, AT_ERR_DOMAIN, "pair %lld: input outside the domain on which the reference is defined", (long long)bad);
+		if (kept > (unsigned long long)n) return fail(h, AT_ERR_RANGE, "at_allpairs_hits: %llu hits kept of the %lld pairs from %lld", kept, (long long)n, (long long)(first_pair + lo));
+		if (kept > 0) {
+			const size_t was = hits.size();
+			hits.resize(was + (size_t)kept);
+			HIP_TRY(h, hipMemcpyAsync(hits.data() + was, drec(q), (size_t)kept * sizeof(at::PairHit), hipMemcpyDeviceToHost, cs));
+			HIP_TRY(h, hipStreamSynchronize(cs));
+		}
+		return AT_OK;
+	};
+	for (int64_t c = 0; c < nchunks; ++c) {
+		const int q = (int)(c & 1);
+		const int64_t lo = c * chunk, n = std::min(chunk, npairs - lo);
+		/* (slice c - 2, the last user of buffer set q, was delivered before slice c - 1 was queued) */
+		rc = align_device(h, mode, n, rs.d_words, rs.bits, rs.d_swoff, rs.d_len, rs.d_swoff, rs.d_len, rs.maxlen, rs.maxlen, 0, 0,
+		                  dres(q, 0), dres(q, 1), dres(q, 2), dres(q, 3), nullptr, nullptr, nullptr, s, nreads, first_pair + lo);
+		if (rc) { (void)hipDeviceSynchronize(); return rc; }
+		if (c == 0) run.cfg0 = h->cfg;
+		at::PairHitsArgs pa;
+		memset(&pa, 0, sizeof pa);
+		pa.n = n; pa.first = first_pair + lo; pa.nreads = nreads;
+		pa.score = dres(q, 0); pa.end_i = dres(q, 1); pa.end_j = dres(q, 2); pa.state = dres(q, 3);
+		pa.threshold = threshold; pa.is_edit = mode == AT_MODE_EDIT ? 1 : 0;
+		pa.flag = d_flag; pa.off = d_off; pa.hits = drec(q); pa.cap = chunk; pa.slots = dslots(q);
+		auto select = [&]() -> int {
+			HIP_TRY(h, hipMemsetAsync(dslots(q), 0xff, 8, s));
+			HIP_TRY(h, at_pairhits_flag_launch(&pa, h->ncu, s));
+			if (int rcs = scan_nops_device(h, n, d_flag, (int64_t *)d_off, s)) return rcs;
+			HIP_TRY(h, at_pairhits_emit_launch(&pa, h->ncu, s));
+			HIP_TRY(h, hipEventRecord(h->ev_sweep[q], s));
+			return AT_OK;
+		};
+		rc = select();
+		if (rc == AT_OK && c >= 1) rc = deliver(c - 1);
+		if (rc) { (void)hipDeviceSynchronize(); return rc; }
+		HIP_TRY(h, hipStreamWaitEvent(cs, h->ev_sweep[q], 0));
+		HIP_TRY(h, hipMemcpyAsync((void *)hslots(q), dslots(q), 16, hipMemcpyDeviceToHost, cs));
+		HIP_TRY(h, hipEventRecord(h->ev_copy[q], cs));
+	}
+	rc = deliver(nchunks - 1);
+	if (rc) return rc;
+	run.nslices = nchunks; run.chunk = chunk;
+	return AT_OK;
+}
+
+/* the alignments of n hits (one piece): pair list and op slots from the records, the sweep with tracebacks, the runs, the check */
+static int pairhits_cigars(at_handle *h, int mode, const ReadSet &rs, const at::PairHit *hits, int64_t n, int64_t ops_bytes, int flags,
+                           int32_t *out_stats, int32_t *out_ncigar, int64_t *p_off, uint32_t *out_cigar, int64_t room, std::string *tbcfg)
+{
+	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	const size_t b8 = al((size_t)(n + 1) * 8), b4 = al((size_t)n * 4), bst = al((size_t)n * 32), brec = al((size_t)n * sizeof(at::PairHit));
+	const int64_t dcap = std::min<int64_t>(room, ops_bytes);   /* (a list has no more runs than ops) */
+	int rc = grow(h, &h->d_out, &h->out_bytes, brec + 3 * b8 + 8 * b4);
+	if (rc) return rc;
+	rc = grow(h, &h->d_str, &h->str_bytes, al((size_t)ops_bytes + 64));
+	if (rc) return rc;
+	rc = grow(h, &h->d_cg, &h->cg_bytes, b4 + bst + b8 + al((size_t)dcap * 4) + 256);
+	if (rc) return rc;
+	char *dw = (char *)h->d_out, *dc = (char *)h->d_cg;
+	at::PairHit *d_rec = (at::PairHit *)dw;
+	int64_t *d_woff1 = (int64_t *)(dw + brec), *d_woff2 = (int64_t *)(dw + brec + b8), *d_ops_off = (int64_t *)(dw + brec + 2 * b8);
+	int32_t *d4[8];
+	for (int x = 0; x < 8; ++x) d4[x] = (int32_t *)(dw + brec + 3 * b8 + (size_t)x * b4);
+	int32_t *d_len1 = d4[0], *d_len2 = d4[1], *d_nslot = d4[2], *d_sc = d4[3], *d_ei = d4[4], *d_ej = d4[5], *d_st = d4[6], *d_nops = d4[7];
+	int32_t *d_ncigar = (int32_t *)dc, *d_stats = (int32_t *)(dc + b4);
+	int64_t *d_coff = (int64_t *)(dc + b4 + bst);
+	uint32_t *d_cigar = (uint32_t *)(dc + b4 + bst + b8);
+	int *d_bad = (int *)(dc + b4 + bst + b8 + al((size_t)dcap * 4));
+	uint8_t *d_ops = (uint8_t *)h->d_str;
+	hipStream_t s = h->stream;
+	HIP_TRY(h, hipMemcpyAsync(d_rec, hits, (size_t)n * sizeof(at::PairHit), hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemsetAsync(d_bad, 0, 4, s));
+	at::PairHitsDescArgs da;
+	memset(&da, 0, sizeof da);
+	da.n = n; da.hits = d_rec; da.swoff = (const long long *)rs.d_swoff; da.slen = rs.d_len;
+	da.woff1 = (long long *)d_woff1; da.woff2 = (long long *)d_woff2; da.len1 = d_len1; da.len2 = d_len2; da.nslot = d_nslot;
+	da.score2 = d_sc; da.end_i2 = d_ei; da.end_j2 = d_ej; da.bad = d_bad;
+	HIP_TRY(h, at_pairhits_desc_launch(&da, h->ncu, s));
+	rc = scan_nops_device(h, n, d_nslot, d_ops_off, s);
+	if (rc) { (void)hipStreamSynchronize(s); return rc; }
+	rc = align_device(h, mode, n, rs.d_words, rs.bits, d_woff1, d_len1, d_woff2, d_len2, rs.maxlen, rs.maxlen, 0, 1, d_sc, d_ei, d_ej, d_st,
+	                  d_ops, d_ops_off, d_nops, s, 0, 0);
+	if (rc) { (void)hipStreamSynchronize(s); return rc; }
+	if (tbcfg && tbcfg->empty()) *tbcfg = h->cfg;
+	rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_ops_off, d_nops, flags, d_ncigar, d_stats, d_coff,
+	                           d_cigar, dcap, s);
+	if (rc) { (void)hipStreamSynchronize(s); return rc; }
+	HIP_TRY(h, at_pairhits_check_launch(&da, h->ncu, s));
+	int bad = 0;
+	HIP_TRY(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipMemcpyAsync(out_ncigar, d_ncigar, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipMemcpyAsync(out_stats, d_stats, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipMemcpyAsync(p_off, d_coff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipStreamSynchronize(s));
+	if (bad) return fail(h, AT_ERR_RANGE, "at_allpairs_hits: the traceback pass does not reproduce a hit's score and end cell");
+	for (int64_t e = 0; e < n; ++e)
+		if (out_ncigar[e] < 0) return fail(h, AT_ERR_DOMAIN, "pair %lld: traceback inconsistent with its sequences", hits[e].pair);
+	/* the words of the hits that end within the caller's room: a prefix of the device buffer */
+	int64_t fit = 0;
+	for (int64_t e = 0; e < n; ++e) if (p_off[e + 1] <= room) fit = p_off[e + 1]; else break;
+	if (fit > 0) {
+		HIP_TRY(h, hipMemcpyAsync(out_cigar, d_cigar, (size_t)fit * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(h, hipStreamSynchronize(s));
+	}
+	return AT_OK;
+}
+
+extern "C" int at_allpairs_hits(at_handle *h, int mode, int64_t nreads,
+                                const uint8_t *seq_blob, const int64_t *off, const int32_t *len,
+                                int64_t first_pair, int64_t npairs, int32_t threshold, int64_t chunk_pairs, int flags,
+                                int64_t hit_cap, int64_t *out_nhits,
+                                int64_t *out_pair, int32_t *out_a, int32_t *out_b,
+                                int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state,
+                                int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
+                                uint32_t *out_cigar, int64_t cigar_cap)
+{
+	int rc = check_allpairs_args(h, "at_allpairs_hits", mode, nreads, first_pair, npairs);
+	if (rc) return rc;
+	if (h->comm) return fail(h, AT_ERR_DOMAIN, "at_allpairs_hits: one GPU only (this handle belongs to a multi-process job)");
+	if (hit_cap < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "at_allpairs_hits: negative capacity");
+	if (flags & ~AT_CIGAR_M) return fail(h, AT_ERR_ARG, "at_allpairs_hits: flags = %d (AT_CIGAR_M or 0)", flags);
+	const bool cg = out_stats || out_ncigar || out_cigar_off || out_cigar;
+	if (cg && (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)))
+		return fail(h, AT_ERR_ARG, "at_allpairs_hits: the CIGAR outputs are either all NULL or all given");
+	if (cg && mode == AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "at_allpairs_hits: edit has no CIGAR here (alignments of edit distances: at_align_batch_cigar)");
+	if (!out_nhits) return fail(h, AT_ERR_ARG, "at_allpairs_hits: NULL argument");
+	if (npairs > 0 && (!seq_blob || !off || !len)) return fail(h, AT_ERR_ARG, "at_allpairs_hits: NULL argument");
+	if (hit_cap > 0 && (!out_pair || !out_a || !out_b || !out_score || !out_end_i || !out_end_j || !out_state))
+		return fail(h, AT_ERR_ARG, "at_allpairs_hits: NULL argument");
+	return guarded(h, "at_allpairs_hits", [&]() -> int {
+		*out_nhits = 0;
+		PairHitsRun run;
+		std::vector<at::PairHit> hits;
+		auto config = [&]() {
+			snprintf(h->cfg, sizeof h->cfg, "allpairs-hits: threshold=%d, %lld slices of <= %lld pairs, kept=%lld; %.300s", threshold,
+			         (long long)run.nslices, (long long)run.chunk, (long long)hits.size(), run.cfg0.empty() ? "none" : run.cfg0.c_str());
+		};
+		if (npairs == 0) {
+			if (cg) out_cigar_off[0] = 0;
+			config();
+			return (int)AT_OK;
+		}
+		ReadSet rs;
+		int rc2 = upload_reads(h, mode, nreads, seq_blob, off, len, &rs);
+		if (rc2) return rc2;
+		{
+			/* overlap: the bit-parallel bound with this call's threshold, whatever at_set_min_score says; that setting is put back at once */
+			struct Keep { at_handle *h; int on, score; ~Keep() { h->min_on = on; h->min_score = score; } } keep = {h, h->min_on, h->min_score};
+			if (mode == AT_MODE_OVERLAP) { h->min_on = 1; h->min_score = threshold; }
+			rc2 = allpairs_hit_slices(h, mode, nreads, rs, first_pair, npairs, chunk_pairs, threshold, hits, run);
+		}
+		if (rc2) return rc2;
+		config();
+		const int64_t nh = (int64_t)hits.size();
+		*out_nhits = nh;
+		if (nh > hit_cap) return (int)AT_OK;               /* the caller comes back with room */
+		for (int64_t e = 0; e < nh; ++e) {
+			const at::PairHit &x = hits[(size_t)e];
+			out_pair[e] = x.pair; out_a[e] = x.a; out_b[e] = x.b;
+			out_score[e] = x.score; out_end_i[e] = x.end_i; out_end_j[e] = x.end_j; out_state[e] = x.state;
+		}
+		if (!cg) return (int)AT_OK;
+		out_cigar_off[0] = 0;
+		if (nh == 0) return (int)AT_OK;
+		/* the traceback pass over the hits, in pieces that keep its descriptor and op buffers moderate */
+		const int64_t piece_hits = 1LL << 20, piece_ops = 1LL << 30;
+		std::vector<int64_t> p_off;
+		std::string tbcfg;
+		for (int64_t a = 0, b; a < nh; a = b) {
+			int64_t ops = 0;
+			for (b = a; b < nh && b - a < piece_hits; ++b) {
+				const int64_t one = (int64_t)len[hits[(size_t)b].a] + len[hits[(size_t)b].b];
+				if (b > a && ops + one > piece_ops) break;
+				ops += one;
+			}
+			const int64_t n = b - a, base = out_cigar_off[a];
+			const int64_t room = std::max<int64_t>(0, cigar_cap - base);
+			p_off.assign((size_t)n + 1, 0);
+			rc2 = pairhits_cigars(h, mode, rs, hits.data() + a, n, ops, flags, out_stats + a * 8, out_ncigar + a, p_off.data(),
+			                      room > 0 ? out_cigar + base : nullptr, room, &tbcfg);
+			if (rc2) return rc2;
+			for (int64_t e = 1; e <= n; ++e) out_cigar_off[a + e] = base + p_off[(size_t)e];
+		}
+		config();
+		cfg_append(h, "; alignments: %.200s, cigars: %d lanes/pair", tbcfg.c_str(), h->last_cigar_lanes);
 		return (int)AT_OK;
 	});
 }

@@ -133,6 +133,10 @@ static int main_single(int cmd, int argc, char *argv[])
  *     --score-only   no tracebacks: one line per pair (name1, name2, score)
  *     --min-score T  (overlap --all-vs-all --score-only) only pairs that score at least T are printed; pairs the bit-parallel
  *                    bound proves below T are not swept at all (at_set_min_score)
+ *     --keep T       (--all-vs-all, with --score-only or --paf) only the pairs that score at least T (edit: whose distance is at
+ *                    most T) leave the GPU (at_allpairs_hits): --score-only prints their lines of the dense run, --paf (not edit)
+ *                    one PAF line each -- query read a, target read b, strand +, cg:Z the =/X CIGAR.  Not with --queries,
+ *                    --gpus N > 1, --min-score, --infix, --alignments, --scan.
  *     --queries Q    every record of Q (a query) against every record of the file (a target); per query, in file order, its best
  *                    --best K (1..64, default 1) hits in rank order -- higher score first, edit: smaller distance first, ties: the
  *                    earlier target -- each printed as a pair line of this command (at_search; strings from at_align_batch_strings
@@ -169,7 +173,7 @@ static int main_single(int cmd, int argc, char *argv[])
  * thread -- which also pays the HIP start-up, in the shadow of the first chunks' parsing -- sends each chunk to the GPU
  * and writes its results with one fwrite.  Memory is bounded by the chunks in flight, whatever the size of the file;
  * --all-vs-all keeps the read set and streams slices of the triangle instead (at_align_allpairs_stream). */
-typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments, infix, scan; int all_hits, max_dist, sep_set, min_sep; } batch_flags;
+typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments, infix, scan; int all_hits, max_dist, sep_set, min_sep; int keep_on, keep; } batch_flags;
 static int g_edit_alignments;   /* --alignments: every handle of this process delivers edit alignments (set before any handle exists) */
 static int g_edit_infix;        /* --infix: every handle of this process is in edit infix mode (at_set_edit_infix; set likewise) */
 
@@ -561,7 +565,45 @@ static int batch_worker(int cmd, opt_t *opt, const batch_flags *bf, const char *
 		roff = (int64_t *)at_xmalloc((size_t)nrec * 8); rlen = (int32_t *)at_xmalloc((size_t)nrec * 4);
 		for (k = 0; k < nrec; ++k) { roff[k] = (int64_t)c.off[k]; rlen[k] = (int32_t)c.len[k]; }
 	}
-	if (!comm && !tb) {
+	if (bf->keep_on) {
+		/* --keep T: only the pairs over the threshold come back (at_allpairs_hits), with --paf together with their CIGARs */
+		int64_t nh = 0, cap = 0, cgcap = 0, k;
+		int64_t *hp = NULL, *cgoff = NULL;
+		int32_t *ha = NULL, *hb = NULL, *hsc = NULL, *hei = NULL, *hej = NULL, *hst = NULL, *stats = NULL, *ncg = NULL;
+		uint32_t *cg = NULL;
+		int turn;
+		for (turn = 0; turn < 3; ++turn) {          /* more hits, then more runs, than there was room for */
+			rc = at_allpairs_hits(h, mode, nrec, c.blob, roff, rlen, 0, npairs, bf->keep, env_i64("AT_CLI_CHUNK", 0), 0, cap, &nh,
+			                      hp, ha, hb, hsc, hei, hej, hst, stats, ncg, cgoff, cg, cgcap);
+			if (rc != AT_OK) die("%s", at_last_error(h));
+			if (nh > cap || turn == 0) {
+				cap = nh;
+				hp = (int64_t *)at_xrealloc(hp, (size_t)(cap + 1) * 8);
+				ha = (int32_t *)at_xrealloc(ha, (size_t)(cap + 1) * 4); hb = (int32_t *)at_xrealloc(hb, (size_t)(cap + 1) * 4);
+				hsc = (int32_t *)at_xrealloc(hsc, (size_t)(cap + 1) * 4); hei = (int32_t *)at_xrealloc(hei, (size_t)(cap + 1) * 4);
+				hej = (int32_t *)at_xrealloc(hej, (size_t)(cap + 1) * 4); hst = (int32_t *)at_xrealloc(hst, (size_t)(cap + 1) * 4);
+				if (bf->paf) {
+					stats = (int32_t *)at_xrealloc(stats, (size_t)(cap + 1) * 32); ncg = (int32_t *)at_xrealloc(ncg, (size_t)(cap + 1) * 4);
+					cgoff = (int64_t *)at_xrealloc(cgoff, (size_t)(cap + 2) * 8);
+					cgcap = 16 * cap + 64;
+					cg = (uint32_t *)at_xrealloc(cg, (size_t)cgcap * 4);
+				}
+				continue;
+			}
+			if (!bf->paf || cgoff[nh] <= cgcap) break;
+			cgcap = cgoff[nh];
+			cg = (uint32_t *)at_xrealloc(cg, (size_t)cgcap * 4);
+		}
+		if (turn == 3) die("--keep: the hits did not settle in three calls");
+		for (k = 0; k < nh; ++k) {
+			const char *na = c.names + c.name_off[ha[k]], *nb = c.names + c.name_off[hb[k]];
+			if (bf->paf) tb_paf(&out, na, rlen[ha[k]], '+', nb, rlen[hb[k]], hsc[k], hei[k], hej[k], stats + 8 * k, cg + cgoff[k], ncg[k]);
+			else tb_pair(&out, na, nb, hsc[k], cmd == C_EDIT, NULL, NULL, 0);
+			if (out.l > ((size_t)8 << 20)) tb_flush(&out);
+		}
+		tb_flush(&out);
+		free(hp); free(ha); free(hb); free(hsc); free(hei); free(hej); free(hst); free(stats); free(ncg); free(cgoff); free(cg);
+	} else if (!comm && !tb) {
 		/* scores of the whole triangle: the reads go up once, the pairs are enumerated on the GPU, slices are printed as they arrive */
 		ava_print ap;
 		memset(&ap, 0, sizeof ap);
@@ -972,9 +1014,9 @@ static int main_batch(int argc, char *argv[], char *argv0)
 {
 	int cmd = -1, k, n = 0;
 	opt_t *opt = init_opt();
-	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, AT_SCAN_SEP_READ};
+	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, AT_SCAN_SEP_READ, 0, 0};
 	char **av = (char **)at_xmalloc((size_t)(argc + 1) * sizeof(char *));
-	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--gpus N] [--paf] [--alignments] [--infix] [--scan] <pairs.fa>\n"
+	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--keep T] [--gpus N] [--paf] [--alignments] [--infix] [--scan] <pairs.fa>\n"
 	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] [--infix] [--scan] [--all-hits D] [--min-sep S] <targets.fa>\n";
 	/* the long flags of the extension are taken out before getopt sees the reference's short options */
 	for (k = 0; k < argc; ++k) {
@@ -982,6 +1024,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (strcmp(argv[k], "--all-vs-all") == 0) bf.all_vs_all = 1;
 		else if (strcmp(argv[k], "--gpus") == 0 && k + 1 < argc) bf.gpus = atoi(argv[++k]);
 		else if (strcmp(argv[k], "--min-score") == 0 && k + 1 < argc) { bf.min_on = 1; bf.min_score = atoi(argv[++k]); }
+		else if (strcmp(argv[k], "--keep") == 0 && k + 1 < argc) { bf.keep_on = 1; bf.keep = atoi(argv[++k]); }
 		else if (strcmp(argv[k], "--queries") == 0 && k + 1 < argc) bf.queries = argv[++k];
 		else if (strcmp(argv[k], "--best") == 0 && k + 1 < argc) { bf.best = atoi(argv[++k]); bf.best_set = 1; }
 		else if (strcmp(argv[k], "--both-strands") == 0) bf.both = 1;
@@ -1000,7 +1043,14 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	/* --queries: refused with what it cannot go with, before any GPU call */
 	{
 		const char *why = NULL;
-		if (bf.all_hits && !bf.scan) why = "--all-hits goes with --scan";
+		if (bf.keep_on && bf.queries) why = "--keep does not go with --queries (it keeps pairs of --all-vs-all)";
+		else if (bf.keep_on && !bf.all_vs_all) why = "--keep goes with --all-vs-all";
+		else if (bf.keep_on && bf.gpus > 1) why = "--keep runs on one GPU: it does not go with --gpus N > 1";
+		else if (bf.keep_on && bf.min_on) why = "--keep does not go with --min-score (it is the threshold)";
+		else if (bf.keep_on && (bf.infix || bf.alignments || bf.scan)) why = "--keep does not go with --infix, --alignments or --scan";
+		else if (bf.keep_on && bf.score_only == bf.paf) why = "--keep needs one of --score-only and --paf";
+		else if (bf.keep_on && bf.paf && cmd == C_EDIT) why = "--keep --paf does not go with edit (edit has no alignment here)";
+		else if (bf.all_hits && !bf.scan) why = "--all-hits goes with --scan";
 		else if (bf.all_hits && bf.best_set) why = "--all-hits does not go with --best (it reports every occurrence)";
 		else if (bf.sep_set && !bf.all_hits) why = "--min-sep goes with --all-hits";
 		else if (bf.all_hits && bf.max_dist < 0) why = "--all-hits D needs D >= 0";
@@ -1025,7 +1075,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (bf.infix && bf.gpus > 1) why = "--infix runs on one GPU: it does not go with --gpus N > 1";
 		else if (bf.paf && cmd == C_EDIT && !bf.alignments && !bf.scan) why = "--paf does not go with edit (edit has no alignment)";
 		else if (bf.paf && bf.score_only) why = "--paf does not go with --score-only (a PAF line needs the traceback)";
-		else if (bf.paf && bf.all_vs_all) why = "--paf does not go with --all-vs-all";
+		else if (bf.paf && bf.all_vs_all && !bf.keep_on) why = "--paf does not go with --all-vs-all";
 		else if (bf.paf && bf.gpus > 1) why = "--paf runs on one GPU: it does not go with --gpus N > 1";
 		if (why) { fprintf(stderr, "%s\n%s", why, usage_line); free(opt); free(av); return 1; }
 	}

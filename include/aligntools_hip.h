@@ -463,6 +463,39 @@ int at_scan_hits(at_handle *h,
                  int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap);
 
 /*
+ * All-vs-all of which only the pairs over a threshold leave the device: the overlap stage of an assembler wants
+ * the few pairs of a read set that overlap, not the dense triangle of scores.  The pairs, their order and s1 = read a, s2 = read b
+ * (a < b) are those of at_align_allpairs; so are the modes and their refusals (fit: AT_ERR_ARG; edit under at_set_edit_infix:
+ * AT_ERR_DOMAIN).  A HIT is a pair of [first_pair, first_pair + npairs) whose exact score is >= threshold -- with AT_MODE_EDIT,
+ * whose distance is <= threshold (the cutoff convention of at_search).  Per hit: out_pair its triangle index, out_a / out_b the two
+ * reads, and score, end cell and state exactly as at_align_allpairs returns them for that pair.  The hits come in ascending pair
+ * order, whatever chunk_pairs is (pairs per slice; <= 0: the default of at_align_allpairs_stream).
+ *   capacity    *out_nhits is ALWAYS complete.  If it exceeds hit_cap nothing else is written and the call returns AT_OK: the caller
+ *               calls again with room (the protocol of at_scan_hits).  Otherwise the seven per-hit arrays (hit_cap entries each)
+ *               hold the hits
+ *   CIGARs      the four CIGAR outputs are all NULL or all given and laid out over the hits as in at_align_batch_cigar: out_stats 8
+ *               per hit, out_cigar_off *out_nhits + 1 entries, the words of the hits that end within cigar_cap; flags: AT_CIGAR_M
+ *               or 0.  The alignments come from a second, traceback pass over the hits only; a pair whose second pass does not
+ *               reproduce its score and end cell makes the call AT_ERR_RANGE.  With AT_MODE_EDIT they must be NULL (AT_ERR_ARG)
+ *   the bound   with AT_MODE_OVERLAP the call engages the bit-parallel bound of at_set_min_score with `threshold` for its duration --
+ *               pairs proven below it are not swept -- and puts the handle's own setting back.  Where the bound does not apply
+ *               (reads over 1 024 bases, reads that need 8-bit words, scoring outside m >= 0, 2 c > m) every pair is swept
+ * Per slice only a count and the kept records cross the link.  One GPU (a handle of a multi-process job: AT_ERR_DOMAIN);
+ * synchronous.  A pair outside the reference's domain makes the call AT_ERR_DOMAIN; the text names the smallest such pair index.
+ * AT_ERR_ARG also for hit_cap < 0, cigar_cap < 0, other flags.  at_last_config: "allpairs-hits: threshold=T, S slices of <= C
+ * pairs, kept=M; " and the first slice's sweep text; with CIGARs "; alignments: " and the traceback pass's text follow.
+ * Not here: reverse-complement or swapped orientations, several GPUs, CIGARs of edit distances, fit.
+ */
+int at_allpairs_hits(at_handle *h, int mode, int64_t nreads,
+                     const uint8_t *seq_blob, const int64_t *off, const int32_t *len,
+                     int64_t first_pair, int64_t npairs, int32_t threshold, int64_t chunk_pairs, int flags,
+                     int64_t hit_cap, int64_t *out_nhits,
+                     int64_t *out_pair, int32_t *out_a, int32_t *out_b,
+                     int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state,
+                     int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
+                     uint32_t *out_cigar, int64_t cigar_cap);
+
+/*
  * Multi-process batches: one process per GPU, each with its own handle.  The pairs are independent, so
  * the only communication is a broadcast of rank 0's scoring block and a gather of results, both RCCL collectives on the
  * handles' devices (over xGMI inside a node).  `dir` is a directory all ranks can reach: rank 0 leaves the RCCL id there.
