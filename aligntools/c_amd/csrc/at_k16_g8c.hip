@@ -3,17 +3,17 @@
  * ceil(l1 / 8) rounded up to one of {5, 6, 7, 8, 10, 13, 16, 19}.  150 x 150: 150 of 152 rows and 150 of 157 steps carry cells
  * (94 percent; four groups of 16 lanes x 10 rows: 85), and the per-step overhead is spread over 19 rows.  The pointer
  * matrix always lives in the per-wave global slots (16 alignments do not fit LDS); this unit: K in {19} */
-template <int MODE, int K>
+template <int MODE, int K, bool PROF = false>
 static at_sweep16_fn h3(bool tb)
 {
-	if (!tb) return at::at_sweep16<MODE, 8, K, 4, true, true, false, false, AT_BITS16>;
-	return at::at_sweep16<MODE, 8, K, 4, true, false, true, false, AT_BITS16>;
+	if (!tb) return at::at_sweep16<MODE, 8, K, 4, true, true, false, false, AT_BITS16, 0, 0, PROF>;
+	return at::at_sweep16<MODE, 8, K, 4, true, false, true, false, AT_BITS16, 0, 0, PROF>;
 }
-template <int MODE>
+template <int MODE, bool PROF = false>
 static at_sweep16_fn h2(int k, bool tb)
 {
 	switch (k) {
-	case 19: return h3<MODE, 19>(tb);
+	case 19: return h3<MODE, 19, PROF>(tb);
 	default: return nullptr;
 	}
 }
@@ -23,6 +23,7 @@ at_sweep16_fn AT_NAME(at_pick16_g8c)(int kmode, int k, int store, bool tb)
 	switch (kmode) {
 	case at::K_GLOBAL: return h2<at::K_GLOBAL>(k, tb);
 	case at::K_LOCAL: return h2<at::K_LOCAL>(k, tb);
+	AT_CASE_LOCAL_PROF(h2<at::K_LOCAL, true>(k, tb))
 	case at::K_FITJ: return h2<at::K_FITJ>(k, tb);
 	default: return h2<at::K_FIT>(k, tb);
 	}

@@ -3,21 +3,21 @@
  * 32 x K rows -- K = 10 (320), 12 (384), 13 (416) for every mode, 16 (512) for local and global, 19 (608) for local (the classes
  * of the uniform kernels, at_k16_g32*.hip).  Frames as in at_k16_rag16b.hip: a work item sweeps the extents its alignments need,
  * every alignment keeps its own.  The pointer matrix lives in the per-wave global slots. */
-template <int MODE, int K>
+template <int MODE, int K, bool PROF = false>
 static at_sweep16_fn y3(bool tb)
 {
-	if (!tb) return at::at_sweep16<MODE, 32, K, 4, true, true, false, true, AT_BITS16>;
-	return at::at_sweep16<MODE, 32, K, 4, true, false, true, true, AT_BITS16>;
+	if (!tb) return at::at_sweep16<MODE, 32, K, 4, true, true, false, true, AT_BITS16, 0, 0, PROF>;
+	return at::at_sweep16<MODE, 32, K, 4, true, false, true, true, AT_BITS16, 0, 0, PROF>;
 }
-template <int MODE>
+template <int MODE, bool PROF = false>
 static at_sweep16_fn y2(int k, bool tb)
 {
 	switch (k) {
-	case 10: return y3<MODE, 10>(tb);
-	case 12: return y3<MODE, 12>(tb);
-	case 13: return y3<MODE, 13>(tb);
-	case 16: if constexpr (MODE == at::K_LOCAL || MODE == at::K_GLOBAL) return y3<MODE, 16>(tb); else return nullptr;
-	case 19: if constexpr (MODE == at::K_LOCAL) return y3<MODE, 19>(tb); else return nullptr;
+	case 10: return y3<MODE, 10, PROF>(tb);
+	case 12: return y3<MODE, 12, PROF>(tb);
+	case 13: return y3<MODE, 13, PROF>(tb);
+	case 16: if constexpr (MODE == at::K_LOCAL || MODE == at::K_GLOBAL) return y3<MODE, 16, PROF>(tb); else return nullptr;
+	case 19: if constexpr (MODE == at::K_LOCAL) return y3<MODE, 19, PROF>(tb); else return nullptr;
 	default: return nullptr;
 	}
 }
@@ -27,6 +27,7 @@ at_sweep16_fn AT_NAME(at_pick16_rag32)(int kmode, int k, int store, bool tb)
 	switch (kmode) {
 	case at::K_GLOBAL: return y2<at::K_GLOBAL>(k, tb);
 	case at::K_LOCAL: return y2<at::K_LOCAL>(k, tb);
+	AT_CASE_LOCAL_PROF(y2<at::K_LOCAL, true>(k, tb))
 	case at::K_FITJ: return y2<at::K_FITJ>(k, tb);
 	default: return y2<at::K_FIT>(k, tb);
 	}

@@ -13,9 +13,10 @@ at_myers_fn at_pick_myers_semi(int w);   /* the overlap filter: one alignment pe
 /* store: 0 = everything in LDS, 1 = s2/boundary in LDS + pointers in the global slot, 2 = everything global */
 at_sweep_fn at_pick32_b2(int kmode, int k, int store, bool tb);
 at_sweep_fn at_pick32_b8(int kmode, int k, int store, bool tb);
-at_sweep16_fn at_pick16_rag(int kmode, int g, int k, int store, bool tb, int bits);   /* ragged frames: g in {8, 16} */
-at_sweep16_fn at_pick16(int kmode, int g, int k, int ts, int store, bool tb, int bits);
-at_sweep16_fn at_pick16_tp(int kmode, int g, int k, int ts, int bits, int split = 0);   /* two-pass tracebacks (CK kernels; split = 1: pass 2 is a kernel of its own), or nullptr */
+/* (prof: the local kernel with the profile lookup -- 2-bit words and scores x16 only; every local kernel of those units has both forms) */
+at_sweep16_fn at_pick16_rag(int kmode, int g, int k, int store, bool tb, int bits, bool prof = false);   /* ragged frames: g in {8, 16} */
+at_sweep16_fn at_pick16(int kmode, int g, int k, int ts, int store, bool tb, int bits, bool prof = false);
+at_sweep16_fn at_pick16_tp(int kmode, int g, int k, int ts, int bits, int split = 0, bool prof = false);   /* two-pass tracebacks (CK kernels; split = 1: pass 2 is a kernel of its own), or nullptr */
 typedef void (*at_walk16_fn)(const at::Sweep16Args, const at::Sweep16Args);   /* (launch, its sliver) */
 at_walk16_fn at_pick_walk16(int kmode, int g, int k, int ts, int bits, int teams = 0);   /* their pass 2 as a kernel of its own (at_walk16.hip.h; teams: several lanes per pair of alignments -- the 64-lane groups), or nullptr */
 int at_walk16_team_lanes(int g);
@@ -26,6 +27,15 @@ int at_walk16_team_lanes(int g);
 #endif
 #define AT_CAT_(a, b) a##b
 #define AT_CAT(a, b) AT_CAT_(a, b)
+/* The local kernels of the 2-bit units with scores x16 exist twice: with the score LUT, and (PROF, at_sweep16.hip.h) with the step's
+ * profile words for the scorings of at::profile_lookup_ok.  The pickers of at_k16.hip name the second kind with this bit on kmode, and
+ * only towards units that hold it; a unit adds its case with AT_CASE_LOCAL_PROF (nothing in the byte build). */
+constexpr int AT_KMODE_PROF = 0x100;
+#if AT_BITS16 == 2
+#define AT_CASE_LOCAL_PROF(...) case at::K_LOCAL | AT_KMODE_PROF: return __VA_ARGS__;
+#else
+#define AT_CASE_LOCAL_PROF(...)
+#endif
 #define AT_NAME(f) AT_CAT(f, AT_CAT(_b, AT_BITS16))   /* g: lanes per group (64 or 16); ts: 4 (x16) or 2 (x4) */   /* kmode in {K_GLOBAL, K_LOCAL, K_FIT} */
 
 template <int MODE, int BITS, int K>

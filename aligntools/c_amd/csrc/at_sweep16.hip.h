@@ -291,6 +291,84 @@ constexpr bool xor3_proof()
 static_assert(xor3_proof(), "XOR3 cells: the decode returns m's state, `L extended` and `U extended` for all 16 inputs");
 static_assert(PtrTags<K_GLOBAL, 4, 0>::L == 15 && PtrTags<K_LOCAL, 4, 16>::M == 10 && PtrTags<K_LOCAL, 2, 0>::L == 3 && PtrTags<K_FIT, 4, 0>::U == 1, "every other family keeps its tags");
 
+/* Local 2-bit batches whose scoring has m >= 0 >= u and D = (m - u) * 16 <= 255 (PROF kernels; the host routes, profile_lookup_ok):
+ * the diagonal candidate max(0, X + S) in three instructions instead of four.  A match is symmetric, so the profile belongs to the
+ * STEP: PA = D << (8 * a) holds D in byte a (a = this step's s2 code of alignment A -- staged premultiplied by 8, so one SDWA shift
+ * with a byte operand builds it), PB likewise, and the row's constant selector {0x0c, 4 + qB, 0x0c, qA} reads D where the query base
+ * equals the step's and 0 elsewhere:
+ *   S' = v_perm_b32(PB, PA, psel[r])         D or 0, per half
+ *   t  = v_pk_add_u16(diag, S')              X >= 0 in local mode and the host's range check keep the sum below 2^15
+ *   M  = v_pk_sub_u16(t, |u| * 16) clamp     = diag + m*16 for a match, diag + u*16 for a mismatch, and the unsigned saturation is
+ *                                            the max(..., 0): a clamped half is 0x0000 -- value 0, tag HOME -- as with v_pk_max_i16
+ * D and u * 16 are multiples of 16: the tag nibble of diag survives exactly when the value does. */
+__host__ __device__ constexpr bool profile_lookup_ok(int m, int u) { return m >= 0 && u <= 0 && (m - u) * 16 <= 255; }
+__host__ __device__ constexpr uint32_t prof_word(uint32_t d, uint32_t code8) { return d << (code8 & 31u); }   /* code8 = 8 * the s2 code */
+__host__ __device__ constexpr uint32_t prof_sel(uint32_t qa, uint32_t qb) { return qa | (qb << 16) | 0x0c040c00u; }
+/* ... spelled out per 16-bit half, for the proof below */
+constexpr uint32_t prof_perm_half(uint32_t word, uint32_t q) { return (word >> (8 * q)) & 0xffu; }
+constexpr uint32_t prof_m_half(uint32_t diag, uint32_t sp, uint32_t nu)
+{
+	const uint32_t t = (diag + sp) & 0xffffu;
+	return t > nu ? t - nu : 0u;
+}
+constexpr uint32_t old_m_half(uint32_t diag, int s)   /* pmax(padd(diag, S), 0) */
+{
+	int v = (int)(short)diag + s;
+	v = v > 32767 ? 32767 : v < -32768 ? -32768 : v;
+	return (uint32_t)(v > 0 ? v : 0);
+}
+/* the lookup (D where the query base is the step's, 0 elsewhere) and, for every diag in [lo, hi) -- any value >= 0 with any tag nibble -- whose
+ * sum the signed add does not saturate (the host's range check keeps |score| * 16 below 2^15), both outcomes of S' */
+constexpr bool prof_proof(int m, int u, uint32_t lo, uint32_t hi)
+{
+	if (!profile_lookup_ok(m, u)) return false;
+	const int m16 = m * 16, u16 = u * 16;
+	const uint32_t d = (uint32_t)(m16 - u16), nu = (uint32_t)(-u16);
+	for (uint32_t a = 0; a < 4; ++a)
+		for (uint32_t q = 0; q < 4; ++q)
+			if (prof_perm_half(prof_word(d, 8 * a), q) != (a == q ? d : 0u)) return false;
+	for (uint32_t diag = lo; diag < hi && (int)diag + m16 <= 32767; ++diag)
+		if (prof_m_half(diag, d, nu) != old_m_half(diag, m16) || prof_m_half(diag, 0u, nu) != old_m_half(diag, u16)) return false;
+	return true;
+}
+/* u and D at the ends of their ranges: m = 0, u = 0, D = 0, D = 240 (the last multiple of 16 in a byte) from either side; in pieces of
+ * 4 096 values of diag, each inside the compiler's budget for one constant expression */
+#define AT_PROF_PROOF_(m, u, q) static_assert(prof_proof(m, u, (q) * 0x1000u, ((q) + 1) * 0x1000u), "profile lookup: add, subtract-and-clamp equals pmax(padd(diag, S), 0) bit for bit");
+#define AT_PROF_PROOF(m, u) AT_PROF_PROOF_(m, u, 0) AT_PROF_PROOF_(m, u, 1) AT_PROF_PROOF_(m, u, 2) AT_PROF_PROOF_(m, u, 3) AT_PROF_PROOF_(m, u, 4) AT_PROF_PROOF_(m, u, 5) AT_PROF_PROOF_(m, u, 6) AT_PROF_PROOF_(m, u, 7)
+AT_PROF_PROOF(0, 0) AT_PROF_PROOF(15, 0) AT_PROF_PROOF(0, -15) AT_PROF_PROOF(8, -7) AT_PROF_PROOF(1, -14) AT_PROF_PROOF(2, -2)
+#undef AT_PROF_PROOF
+#undef AT_PROF_PROOF_
+static_assert(prof_sel(3, 2) == 0x0c060c03u && !profile_lookup_ok(8, -8) && !profile_lookup_ok(-1, -2) && !profile_lookup_ok(1, 1), "the selector's bytes; the scorings that keep the LUT");
+/* PA / PB of step kk of a window word (bytes 8 * code): v_lshlrev_b32 with an SDWA byte operand, one instruction */
+template <int KK>
+AT_DEV uint32_t prof_word_v(uint32_t win, uint32_t d)
+{
+	uint32_t r;
+	if constexpr (KK == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "=v"(r) : "v"(win), "v"(d));
+	else if constexpr (KK == 1) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD" : "=v"(r) : "v"(win), "v"(d));
+	else if constexpr (KK == 2) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD" : "=v"(r) : "v"(win), "v"(d));
+	else asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD" : "=v"(r) : "v"(win), "v"(d));
+	return r;
+}
+/* (asm: left to itself hipcc may turn the pair into signed saturating forms with a maximum behind them.  nu2 = |u| * 16 in both halves is the
+ * same in every lane and rides in a scalar register: held in a vector register like the other constants, the 8-lane kernel with pointers
+ * came out with a private segment of 68 bytes that no instruction touches, and waves with a private segment start more slowly) */
+AT_DEV uint32_t prof_m_v(uint32_t diag, uint32_t pb, uint32_t pa, uint32_t psel, uint32_t nu2)
+{
+	uint32_t t, m;
+	const uint32_t sp = __builtin_amdgcn_perm(pb, pa, psel);
+	asm("v_pk_add_u16 %0, %1, %2" : "=v"(t) : "v"(diag), "v"(sp));
+	asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(m) : "v"(t), "s"(nu2));
+	return m;
+}
+/* the four s2 codes of a sequence byte as staged bytes: the code, or 8 * the code for the PROF kernels */
+template <bool PROF>
+AT_DEV uint32_t s2_bytes(uint32_t b)
+{
+	if constexpr (PROF) return ((b & 3u) << 3) | ((b & 0xcu) << 9) | ((b & 0x30u) << 15) | ((b & 0xc0u) << 21);
+	else return (b & 3u) | ((b & 0xcu) << 6) | ((b & 0x30u) << 12) | ((b & 0xc0u) << 18);
+}
+
 template <bool LDS, int K>
 AT_DEV int pidx(int wr, int r, int lane, int NL)
 {
@@ -509,7 +587,7 @@ AT_DEV uint2 ck_entry(uint32_t eL, uint32_t eM, uint32_t eU, uint32_t eJ, uint32
 #else
 #define AT_REPLAY_FN __device__ __noinline__
 #endif
-template <int MODE, int G, int K, int TS, bool SMALL, int BITS, int CB>
+template <int MODE, int G, int K, int TS, bool SMALL, int BITS, int CB, bool PROF = false>
 AT_REPLAY_FN void replay16_block(const Sweep16Args &a, const Slot<SMALL> &mem, uint32_t *gs, const int refoff,
                            const uint32_t *qA, const uint32_t *qB, const int l1A, const int l1B,
                            const int blA, const int cA, const int blB, const int cB)
@@ -534,6 +612,10 @@ AT_REPLAY_FN void replay16_block(const Sweep16Args &a, const Slot<SMALL> &mem, u
 	uint32_t gmo2 = pk2(a.g16 - a.o16), neg2 = 0x80008000u;
 	uint32_t c1 = 0x00010001u, umm2 = pk2(a.u16 - a.m16), m2 = pk2(a.m16);
 	asm volatile("" : "+v"(c8888), "+v"(gmo2), "+v"(neg2), "+v"(c1), "+v"(umm2), "+v"(m2));
+	if constexpr (PROF) lut_lo = (uint32_t)(a.m16 - a.u16);   /* PROF: D in the LUT's place; |u| * 16 in a scalar register (prof_m_v) */
+	const uint32_t &profD = lut_lo;
+	const uint32_t nu2 = pk2(-a.u16);
+	(void)profD; (void)nu2;
 	asm volatile("" : "+v"(o2), "+v"(e2), "+v"(lut_lo), "+v"(lut_hi));
 	asm volatile("" : "+v"(cClean), "+v"(cTagM), "+v"(cTagL), "+v"(cTagU), "+v"(cM3), "+v"(cM7), "+v"(cF0), "+v"(cF000));
 
@@ -623,7 +705,7 @@ AT_REPLAY_FN void replay16_block(const Sweep16Args &a, const Slot<SMALL> &mem, u
 			uint32_t ca, cb;
 			if constexpr (BITS == 2) { ca = (wa >> ((qi & 15) * 2)) & 3u; cb = (wb >> ((qj & 15) * 2)) & 3u; }
 			else { ca = (wa >> ((qi & 3) * 8)) & 0xffu; cb = (wb >> ((qj & 3) * 8)) & 0xffu; }
-			qsel[r] = (ca * 0x00000101u + cb * 0x01010000u) | (BITS == 2 ? 0x04000400u : 0u);
+			qsel[r] = PROF ? prof_sel(ca, cb) : (ca * 0x00000101u + cb * 0x01010000u) | (BITS == 2 ? 0x04000400u : 0u);
 			acc[r] = 0;
 		}
 	}
@@ -655,17 +737,23 @@ AT_REPLAY_FN void replay16_block(const Sweep16Args &a, const Slot<SMALL> &mem, u
 			const uint32_t Aup = eup.x, Bup = eup.y;
 			uint32_t gopen = neg2;
 			if constexpr (HASJ) gopen = lohi(((smA >> k) & 1u) ? gmo2 : neg2, ((smB >> k) & 1u) ? gmo2 : neg2);
-			const uint32_t selw = __builtin_amdgcn_perm(wB, wA, SELK);
+			uint32_t selw = 0, profA = 0, profB = 0;
+			(void)selw; (void)profA; (void)profB;
+			if constexpr (PROF) { profA = prof_word_v<k>(wA, profD); profB = prof_word_v<k>(wB, profD); }
+			else selw = __builtin_amdgcn_perm(wB, wA, SELK);
 			uint32_t diag = Ad, lraw = Bup, jn = 0;
 			(void)jn;
 #pragma unroll
 			for (int r = 0; r < K; ++r) {
 				/* (the row-step of the one-pass kernels with pointers, sweep16_items: same candidates, same tags, same cells) */
-				uint32_t S;
+				uint32_t S = 0, Mraw;
+				if constexpr (PROF) Mraw = prof_m_v(diag, profB, profA, qsel[r], nu2);
+				else {
 				if constexpr (BITS == 2) S = __builtin_amdgcn_perm(lut_hi, lut_lo, selw ^ qsel[r]);
 				else S = pmad(pminu(selw ^ qsel[r], c1), umm2, m2);
-				uint32_t Mraw = padd(diag, S);
+				Mraw = padd(diag, S);
 				if constexpr (MODE == K_LOCAL) Mraw = pmax(Mraw, 0u);
+				}
 				const uint32_t Mc = vandor(Mraw, cClean, cTagM);
 				const uint32_t Lc = lraw | cTagL;
 				const uint32_t Uraw = pmax(Mo_l[r], padd(U_l[r], e2));
@@ -731,9 +819,12 @@ AT_REPLAY_FN void replay16_block(const Sweep16Args &a, const Slot<SMALL> &mem, u
 
 /* The work items [wbase, wbase + items of `a`) of one launch, pulled from the launch's work counter: `wnext` is the item this wave
  * holds when it gets here (its block index, or what an earlier call left over); returns the first item beyond the range. */
-template <int MODE, int G, int K, int TS, bool SMALL, bool PTRLDS, bool TB, bool RAG = false, int BITS = 2, int CK = 0, int SPLIT = 0>
+template <int MODE, int G, int K, int TS, bool SMALL, bool PTRLDS, bool TB, bool RAG = false, int BITS = 2, int CK = 0, int SPLIT = 0, bool PROF = false>
 AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long long wbase)
 {
+	/* PROF: the diagonal candidate of a local 2-bit sweep by the step's profile words (prof_m_v above; the host sends a scoring here
+	 * only if profile_lookup_ok) -- one step body per kernel, so the scorings outside keep kernels of their own */
+	static_assert(!PROF || (MODE == K_LOCAL && BITS == 2 && TS == 4), "profile lookup: local, 2-bit codes, scores x16");
 	/* SPLIT = 1: pass 2 of the two-pass tracebacks is a kernel of its own (at_walk16.hip.h): this one ends where the rounds would begin */
 	static_assert(!SPLIT || CK > 0, "a walk kernel follows a sweep that leaves checkpoints");
 	/* CK > 0: two-pass tracebacks -- the scores-only sweep leaves checkpoints every CK steps, the pointers are rebuilt block by block
@@ -816,6 +907,10 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 	asm volatile("" : "+v"(gmo2), "+v"(neg2));
 	uint32_t c1 = 0x00010001u, umm2 = pk2(a.u16 - a.m16), m2 = pk2(mS);       /* 8-bit alphabets: compare instead of LUT */
 	asm volatile("" : "+v"(c1), "+v"(umm2), "+v"(m2));
+	if constexpr (PROF) lut_lo = (uint32_t)(a.m16 - a.u16);   /* PROF: D takes a register of the LUT; |u| * 16 rides in a scalar one (prof_m_v) */
+	const uint32_t &profD = lut_lo;
+	const uint32_t nu2 = pk2(-a.u16);
+	(void)profD; (void)nu2;
 	asm volatile("" : "+v"(o2), "+v"(e2), "+v"(lut_lo), "+v"(lut_hi));
 	if constexpr (X3) asm volatile("" : "+v"(cClean), "+v"(cTagM), "+v"(cTagL), "+v"(cTagU), "+v"(cNib), "+v"(cF0), "+v"(cF000));   /* (no cell masks to hold) */
 	else asm volatile("" : "+v"(cClean), "+v"(cTagM), "+v"(cTagL), "+v"(cTagU), "+v"(cM3), "+v"(cM7), "+v"(cNib), "+v"(cF0), "+v"(cF000));
@@ -921,8 +1016,8 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 #pragma unroll
 					for (int q = 0; q < 4; ++q) {
 						const uint32_t ba = (va >> (8 * q)) & 0xffu, bb = (vb >> (8 * q)) & 0xffu;
-						mem.st(refoff + PADW + 4 * w + q, (ba & 3u) | ((ba & 0xcu) << 6) | ((ba & 0x30u) << 12) | ((ba & 0xc0u) << 18));
-						mem.st(refoff + a.off_refb + PADW + 4 * w + q, (bb & 3u) | ((bb & 0xcu) << 6) | ((bb & 0x30u) << 12) | ((bb & 0xc0u) << 18));
+						mem.st(refoff + PADW + 4 * w + q, s2_bytes<PROF>(ba));
+						mem.st(refoff + a.off_refb + PADW + 4 * w + q, s2_bytes<PROF>(bb));
 					}
 				}
 			}
@@ -972,8 +1067,9 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 				if constexpr (BITS == 2) { ca = (qA[qi >> 4] >> ((qi & 15) * 2)) & 3u; cb = (qB[qj >> 4] >> ((qj & 15) * 2)) & 3u; }
 				else { ca = (qA[qi >> 2] >> ((qi & 3) * 8)) & 0xffu; cb = (qB[qj >> 2] >> ((qj & 3) * 8)) & 0xffu; }
 				/* my query bases of both alignments as the bytes {qB|4, qB, qA|4, qA}: xor-ing the s2 bytes {b,b,a,a}
-				 * onto it gives the LUT selector directly (codes are < 4, so the |4 survives the xor) */
-				qsel[r] = (ca * 0x00000101u + cb * 0x01010000u) | (BITS == 2 ? 0x04000400u : 0u);
+				 * onto it gives the LUT selector directly (codes are < 4, so the |4 survives the xor).  PROF: the selector
+				 * {0x0c, 4 + qB, 0x0c, qA} that reads the step's profile words */
+				qsel[r] = PROF ? prof_sel(ca, cb) : (ca * 0x00000101u + cb * 0x01010000u) | (BITS == 2 ? 0x04000400u : 0u);
 				acc[r] = 0;                       /* (steps outside the matrix leave their bits as they are: never read) */
 				/* rows past l1 (only in the last lane that owns rows): their key collapses to the bare row tag,
 				 * which every real row of the lane beats (smaller r = larger tag, score >= 0) */
@@ -1106,7 +1202,10 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 							}
 						}
 						/* step k's byte of each window against each of my query bases */
-						const uint32_t selw = __builtin_amdgcn_perm(wB[hw], wA[hw], SELK);   /* [b, b, a, a] */
+						uint32_t selw = 0, profA = 0, profB = 0;
+						(void)selw; (void)profA; (void)profB;
+						if constexpr (PROF) { profA = prof_word_v<kk>(wA[hw], profD); profB = prof_word_v<kk>(wB[hw], profD); }   /* D in the byte of this step's base */
+						else selw = __builtin_amdgcn_perm(wB[hw], wA[hw], SELK);   /* [b, b, a, a] */
 						uint32_t diag = Ad, lraw = Bup, up = 0, cmax[NCH];
 						uint32_t capmask = 0;
 						if constexpr (RAG && MODE == K_GLOBAL) {
@@ -1120,8 +1219,10 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 #pragma unroll
 						for (int r = 0; r < K; ++r) {
 							/* x = s2 byte ^ query byte (0 = match): selector {xB+4, xB, xA+4, xA} -> the two 16-bit scores */
-							uint32_t S;
-							if constexpr (BITS == 2) {
+							uint32_t S = 0;
+							if constexpr (PROF) {
+								/* (S is folded into Mraw below) */
+							} else if constexpr (BITS == 2) {
 								S = __builtin_amdgcn_perm(lut_hi, lut_lo, selw ^ qsel[r]);
 							} else {
 								/* bytes: x = {b^qB, b^qB, a^qA, a^qA}; per 16-bit half 0 = match.  z = min(x, 1), S = m + z * (u - m) */
@@ -1157,8 +1258,12 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 								Xl[(k & 1) ^ 1][r] = Mcl;
 								continue;
 							}
-							uint32_t Mraw = padd(diag, S);
-							if constexpr (MODE == K_LOCAL) Mraw = pmax(Mraw, 0u);
+							uint32_t Mraw;
+							if constexpr (PROF) Mraw = prof_m_v(diag, profB, profA, qsel[r], nu2);   /* max(0, diag + S) in three instructions */
+							else {
+								Mraw = padd(diag, S);
+								if constexpr (MODE == K_LOCAL) Mraw = pmax(Mraw, 0u);
+							}
 							const uint32_t Mc = TB ? vandor(Mraw, cClean, cTagM) : Mraw;
 							const uint32_t Lc = !TB ? lraw : X3 ? vandor(lraw, cClean, cTagL) : (lraw | cTagL);   /* (15 is all ones; 12 is not) */
 							const uint32_t Uraw = pmax(Mo_l[r], padd(U_l[r], e2));
@@ -1502,7 +1607,7 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 				}
 				long long st_a = 0;
 				if (AT_TP_STATS) { st_a = (long long)__builtin_amdgcn_s_memtime(); ++st_rounds; }
-				replay16_block<MODE, G, K, TS, SMALL, BITS, CK>(a, mem, gs, refoff, qA, qB, l1A, l1B, blk_bl[0], blk_c[0], blk_bl[1], blk_c[1]);
+				replay16_block<MODE, G, K, TS, SMALL, BITS, CK, PROF>(a, mem, gs, refoff, qA, qB, l1A, l1B, blk_bl[0], blk_c[0], blk_bl[1], blk_c[1]);
 				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        /* the blocks' pointer words are in the L2 */
 				if (AT_TP_STATS) st_rep += (long long)__builtin_amdgcn_s_memtime() - st_a;
 				/* (the replay's staging area in LDS is free again: every walker copies the block it is in -- K x CK cells, KQ * CK words [+ the
@@ -1879,16 +1984,16 @@ constexpr int at_tail_k(int g, int k)
  * long) that follow the main items in the same work queue -- a launch that has the chip to itself then ends with a fifth of the
  * SIMDs busy for a short item instead of a tenth of them working through one long item more (C2: 6 250 items of 16 pairs on 2 048
  * resident waves = 3.05 rounds).  t.npairs = 0: no sliver.  Other kernels ignore `t`. */
-template <int MODE, int G, int K, int TS, bool SMALL, bool PTRLDS, bool TB, bool RAG = false, int BITS = 2, int CK = 0, int SPLIT = 0>
+template <int MODE, int G, int K, int TS, bool SMALL, bool PTRLDS, bool TB, bool RAG = false, int BITS = 2, int CK = 0, int SPLIT = 0, bool PROF = false>
 __global__ __launch_bounds__(64, (CK > 0 && G == 64 ? AT_TP_WAVES64 : AT_WAVES16(G, K))) void at_sweep16(const Sweep16Args a, const Sweep16Args t)
 {
 	if (a.only_if && __builtin_amdgcn_readfirstlane(*a.only_if) != a.only_val) return;
-	long long w = sweep16_items<MODE, G, K, TS, SMALL, PTRLDS, TB, RAG, BITS, CK, SPLIT>(a, (long long)blockIdx.x, 0);
+	long long w = sweep16_items<MODE, G, K, TS, SMALL, PTRLDS, TB, RAG, BITS, CK, SPLIT, PROF>(a, (long long)blockIdx.x, 0);
 	if constexpr (G <= 16 && !RAG && MODE != K_OVERLAP) {
 		if (t.npairs > 0) {
 			constexpr int NGm = 64 / G;
 			const long long nmain = (a.npairs + 2 * NGm - 1) / (2 * NGm);
-			sweep16_items<MODE, AT_TAIL_G, at_tail_k(G, K), TS, SMALL, PTRLDS, TB, false, BITS, CK, SPLIT>(t, w, nmain);
+			sweep16_items<MODE, AT_TAIL_G, at_tail_k(G, K), TS, SMALL, PTRLDS, TB, false, BITS, CK, SPLIT, PROF>(t, w, nmain);
 		}
 	}
 }
