@@ -105,6 +105,10 @@ struct at_handle {
 	int infix_anchor = 0;           /* inside at_scan_hits' window pass only: infix alignments end in (l1, l2) (InfixArgs::anchor_end) */
 	/* device scratch (grow-only) */
 	uint32_t *d_sitemask = nullptr; size_t sitemask_words = 0; int sitemask_for_l2 = -1; bool sitemask_dirty = true;
+	/* the site mask's way up: page-locked buffers used in turn, each with the event behind its copy (ensure_sitemask) */
+	struct SiteStage { void *host = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; };
+	std::vector<SiteStage> site_stage;
+	unsigned site_next = 0;
 	uint32_t *d_ws = nullptr; size_t ws_bytes = 0;
 	uint32_t *d_ck = nullptr; size_t ck_bytes = 0;   /* two-pass tracebacks with a walk kernel: a launch's checkpoints */
 	bool ck_alloc_failed = false;                    /* ... could not be allocated once: this handle keeps to the rounds inside the sweep's kernel
@@ -263,6 +267,10 @@ extern "C" void at_destroy(at_handle *h)
 	h->kids.clear();
 	(void)hipSetDevice(h->device);
 	if (h->d_sitemask) (void)hipFree(h->d_sitemask);
+	for (at_handle::SiteStage &c : h->site_stage) {
+		if (c.done) (void)hipEventDestroy(c.done);
+		if (c.host) (void)hipHostFree(c.host);
+	}
 	if (h->d_ws) (void)hipFree(h->d_ws);
 	if (h->d_ck) (void)hipFree(h->d_ck);
 	if (h->d_queue) (void)hipFree(h->d_queue);
@@ -729,12 +737,35 @@ static int grow_pinned(at_handle *h, void **p, size_t *have, size_t need)
 	return AT_OK;
 }
 
+/* The mask goes up from page-locked memory with an event behind the copy, so the host waits for nothing: a caller who changes the
+ * scoring between two launches queued on one stream keeps both queued.  (It used to go up from a temporary, with a wait for the
+ * whole stream behind the copy: every fit -s launch after at_set_scoring stalled the host until the launches before it had
+ * drained.)  A staging buffer is written again only once its event has passed; with AT_SITE_STAGES uploads pending the host waits
+ * for the oldest.  The device copy is ordered like any other use of the handle's buffers: by the stream. */
+enum { AT_SITE_STAGES = 8 };
 static int ensure_sitemask(at_handle *h, int max_l2, hipStream_t stream)
 {
 	if (!h->sitemask_dirty && h->sitemask_for_l2 >= max_l2) return AT_OK;
 	const size_t nbits = (size_t)max_l2 + 64 + 64 + 128;
 	const size_t nw = (nbits + 31) / 32 + 2;
-	std::vector<uint32_t> m(nw, 0xffffffffu);
+	at_handle::SiteStage *st = nullptr;
+	for (at_handle::SiteStage &c : h->site_stage)
+		if (hipEventQuery(c.done) == hipSuccess) { st = &c; break; }
+	(void)hipGetLastError();   /* ("not ready" is an answer, not a failure for the launch check to find) */
+	if (!st && h->site_stage.size() < AT_SITE_STAGES) {
+		at_handle::SiteStage c;
+		HIP_TRY(h, hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
+		h->site_stage.push_back(c);
+		st = &h->site_stage.back();
+	}
+	if (!st) {
+		st = &h->site_stage[h->site_next++ % AT_SITE_STAGES];
+		HIP_TRY(h, hipEventSynchronize(st->done));
+	}
+	int rc = grow_pinned(h, &st->host, &st->bytes, nw * 4);
+	if (rc) return rc;
+	uint32_t *m = (uint32_t *)st->host;
+	for (size_t w = 0; w < nw; ++w) m[w] = 0xffffffffu;
 	/* column j (1-based) may open the jump state iff (j-1) is NOT a listed site
 	 * -- the reference's inverted test, alignment.h:659 / SURVEY.md 0.4 */
 	for (int sidx : h->sites) {
@@ -743,11 +774,11 @@ static int ensure_sitemask(at_handle *h, int max_l2, hipStream_t stream)
 		m[(size_t)(j + 64) >> 5] &= ~(1u << ((j + 64) & 31));
 	}
 	void *p = h->d_sitemask; size_t have = h->sitemask_words * 4;
-	int rc = grow(h, &p, &have, nw * 4);
+	rc = grow(h, &p, &have, nw * 4);
 	h->d_sitemask = (uint32_t *)p; h->sitemask_words = have / 4;
 	if (rc) return rc;
-	HIP_TRY(h, hipMemcpyAsync(h->d_sitemask, m.data(), nw * 4, hipMemcpyHostToDevice, stream));
-	HIP_TRY(h, hipStreamSynchronize(stream));   /* m is a temporary */
+	HIP_TRY(h, hipMemcpyAsync(h->d_sitemask, m, nw * 4, hipMemcpyHostToDevice, stream));
+	HIP_TRY(h, hipEventRecord(st->done, stream));
 	h->sitemask_dirty = false;
 	h->sitemask_for_l2 = max_l2;
 	return AT_OK;

@@ -103,6 +103,12 @@ int at_align_batch(at_handle *h, int mode, int64_t npairs,
  * ONE stream at a time (calls queued on the same stream may follow each other
  * without waiting; a call on another stream needs the earlier ones finished --
  * or its own handle, which is how bench.py keeps three launches in flight).
+ * One kind of call makes the host wait although the entry is asynchronous: the first call of a larger shape on a handle.  Its
+ * workspace, checkpoint buffer, scan scratch or site mask (a longer second sequence under fit -s) is then freed and allocated
+ * anew, and hipFree waits for the device -- which is also what keeps a launch that is still queued from losing its buffer.  A
+ * caller who needs launches in flight warms the handle with its largest shapes first, as bench.py does.  at_set_scoring between
+ * two queued launches does not wait: the next fit -s launch sends the new site mask up behind the launches before it
+ * (tests/test_streams_in_flight.py).
  *   d_seq      packed words; bits = 2 (A,C,G,T -> 0..3, 16 bases per int32,
  *              base k of a sequence in bits [2k%32, 2k%32+1] of word k/16) or
  *              bits = 8 (4 bytes per int32, little endian)
