@@ -62,6 +62,10 @@
 #define AT_JPLANE 1       /* fit -s, scores x16: 4-bit pointer cells + a bit plane for the jump state's pointers (5 bits per cell and
                           * alignment instead of 8; 0 = the round-2 byte cells, for A/B runs) */
 #endif
+#ifndef AT_LOCAL_DIET
+#define AT_LOCAL_DIET 3   /* one-pass local x16 kernels below 64 lanes, for A/B runs: 1 = constant strip border, 2 = scalar step number in the
+                           * arg-max fold (0 = the step body as it was) */
+#endif
 #ifndef AT_OVL_BITS
 #define AT_OVL_BITS 2     /* packed overlap: bits per pointer cell (the walk reads 2; 4 = the round-2 nibble cells, for A/B runs) */
 #endif
@@ -201,6 +205,22 @@ AT_DEV uint32_t grp_up1(uint32_t old, uint32_t src)
 	else return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
 }
 
+/* ... with a constant for lane 0 of every group (the one-strip local kernels: the row above the strip is the matrix border, the same
+ * in every column).  lg = lane in group.  One DPP move and one select whatever G is. */
+template <int G>
+AT_DEV uint32_t grp_up1c(uint32_t cst, uint32_t src, int lg)
+{
+	static_assert(G == 32 || G == 16 || G == 8 || G == 4, "groups that sweep one strip");
+	const uint32_t v = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, G == 32 ? 0x138 /* wave_shr:1 */ : 0x111 /* row_shr:1 */, 0xf, 0xf, true);
+	return lg == 0 ? cst : v;
+}
+/* v_bfi_b32 with the value as a scalar operand (wave-uniform) */
+AT_DEV uint32_t vbfi_s(uint32_t mask, uint32_t a, uint32_t b)
+{
+	uint32_t d;
+	asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(mask), "s"(a), "v"(b));
+	return d;
+}
 /* Word (wr, r, lane) of a strip's pointer matrix: wr = block of SPW steps, r = row in lane.  In LDS the lanes of one
  * (wr, r) are adjacent.  In the HBM slot four rows of a lane are adjacent, then the lanes (the last K % 4 rows form a
  * narrower group of their own): a lane stores 16 bytes at once (about K / 4 stores per block instead of K, each covering
@@ -856,6 +876,16 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 	constexpr int OTGL = Tags::L, OTGM = Tags::M, OTGU = Tags::U;
 	constexpr uint32_t XT1 = xor3_table(1), XT2 = xor3_table(2), XT3 = xor3_table(3);   /* the walkers' decode of those cells, per state */
 	constexpr int TGL = TB ? OTGL : 0, TGM = TB ? OTGM : 0, TGU = TB ? OTGU : 0;
+	/* The one-pass local x16 kernels of the groups below 64 lanes (one strip per item) shed two fixed costs of a step:
+	 *   CBORD  the row above the strip is row 0 of a local matrix, L = M = U = 0 in every column (border16): lane 0 of a group takes the two
+	 *          boundary words as constants -- no boundary row in LDS, no load per block, no row_shl move and no copy into the DPP
+	 *          move's destination per step;
+	 *   TSC    the step number of the arg-max fold as the scalar operand of its v_bfi_b32 instead of a v_mov per step.
+	 * The 64-lane kernels sweep several strips, whose boundary rows are real, and keep the code they had.  (A third one, the pointer
+	 * word of four steps gathered with two v_perm_b32 and joined with a shift and a v_bfi_b32 where it is stored -- four instructions
+	 * instead of five -- removed 4.8 M instructions of a C2 launch and made it 5 % slower: profiles/LOG.md I.) */
+	constexpr bool DIET = MODE == K_LOCAL && TS == 4 && CK == 0 && G < 64;
+	constexpr bool CBORD = DIET && (AT_LOCAL_DIET & 1), TSC = DIET && (AT_LOCAL_DIET & 2);
 	/* Jump state with scores x16: the cell keeps the 4 bits of the other modes and the jump state's own pointer (did J open from
 	 * M here?) goes to a BIT PLANE beside the cells -- one word per 4 rows x 4 steps and half -- 5 bits per cell instead of the 8 of a
 	 * byte cell.  (Scores x4 carry score bits in the low nibble of J: they keep the byte cells.) */
@@ -911,7 +941,11 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 	const uint32_t &profD = lut_lo;
 	const uint32_t nu2 = pk2(-a.u16);
 	(void)profD; (void)nu2;
-	asm volatile("" : "+v"(o2), "+v"(e2), "+v"(lut_lo), "+v"(lut_hi));
+	/* (CBORD kernels: the gap scores ride in scalar registers, one scalar operand per packed add.  With them in vector registers the
+	 * 8-lane kernel with pointers keeps a 64-byte stack slot of a spilled argument tuple that no instruction touches -- a private segment
+	 * again, see prof_m_v; profiles/r15/resources.txt) */
+	if constexpr (CBORD) asm volatile("" : "+s"(o2), "+s"(e2), "+v"(lut_lo), "+v"(lut_hi));
+	else asm volatile("" : "+v"(o2), "+v"(e2), "+v"(lut_lo), "+v"(lut_hi));
 	if constexpr (X3) asm volatile("" : "+v"(cClean), "+v"(cTagM), "+v"(cTagL), "+v"(cTagU), "+v"(cNib), "+v"(cF0), "+v"(cF000));   /* (no cell masks to hold) */
 	else asm volatile("" : "+v"(cClean), "+v"(cTagM), "+v"(cTagL), "+v"(cTagU), "+v"(cM3), "+v"(cM7), "+v"(cNib), "+v"(cF0), "+v"(cF000));
 	const int nstrips = (l1 + RS - 1) / RS;   /* host guarantees 1 when G < 64 */
@@ -1026,13 +1060,24 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 			for (int w = lane; w < a.nsm; w += 64) mem.st(a.off_sm + w, a.sitemask[w]);
 		}
 		/* ---- boundary row 0 (identical for every alignment of the batch) ---- */
-		for (int j = lane; j <= l2; j += 64) {
+		if constexpr (!CBORD) {
+			for (int j = lane; j <= l2; j += 64) {
+				int L, M, U;
+				border16<MODE>(0, j, o16, e16, L, M, U);
+				int x = imax3(L | TGL, M | TGM, U | TGU);
+				const int ld = imax(sat16((L | TGL) + e16), sat16((M | TGM) + o16));
+				if constexpr (OVL) x = j == 0 ? 0 : kNeg16;        /* M(0,j) = -inf, then M(i,0) = 0 for all i (:937-938) */
+				mem.st2(a.off_bound + 2 * j, pk2(x), pk2(ld));
+			}
+		}
+		/* CBORD: the same two words in every column -- what the loop above would store for a local matrix */
+		uint32_t bxC = 0, blC = 0;
+		(void)bxC; (void)blC;
+		if constexpr (CBORD) {
 			int L, M, U;
-			border16<MODE>(0, j, o16, e16, L, M, U);
-			int x = imax3(L | TGL, M | TGM, U | TGU);
-			const int ld = imax(sat16((L | TGL) + e16), sat16((M | TGM) + o16));
-			if constexpr (OVL) x = j == 0 ? 0 : kNeg16;        /* M(0,j) = -inf, then M(i,0) = 0 for all i (:937-938) */
-			mem.st2(a.off_bound + 2 * j, pk2(x), pk2(ld));
+			border16<MODE>(0, 1, o16, e16, L, M, U);
+			bxC = pk2(imax3(L | TGL, M | TGM, U | TGU));
+			blC = pk2(imax(sat16((L | TGL) + e16), sat16((M | TGM) + o16)));
 		}
 		mem.sync();
 
@@ -1114,14 +1159,14 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 				const uint2 v = mem.ld2(a.off_bound + 2 * jn);
 				bx = v.x; bl = v.y;
 			};
-			uint32_t bx, bl, bxn, bln;
-			load_bound(0, bx, bl);
+			uint32_t bx = 0, bl = 0, bxn = 0, bln = 0;
+			if constexpr (!CBORD) load_bound(0, bx, bl);
 			const int ptr_base = a.off_ptr + s * wps * NL;
 
 			for (int blk = 0; blk < tbk; ++blk) {
 				const int t0 = blk * BLK;
 				if constexpr (TP) ck_p = a.off_rck + ck_rck_word<ES>(t0 + 1, lane);
-				load_bound(t0 + BLK, bxn, bln);
+				if constexpr (!CBORD) load_bound(t0 + BLK, bxn, bln);
 				/* ---- s2 windows: bytes t0-lg .. t0-lg+7 of both alignments ---- */
 				uint32_t wA[2], wB[2];
 				{
@@ -1155,9 +1200,11 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 					constexpr uint32_t SELK = (uint32_t)kk * 0x00000101u + (uint32_t)(4 + kk) * 0x01010000u;
 					const int t = t0 + k;
 					uint32_t tpk = pk2(t);
-					asm("" : "+v"(tpk));
-					const uint32_t Aup = grp_up1<G>((uint32_t)row_shl<k>((int)bx), A_prev);
-					const uint32_t Bup = grp_up1<G>((uint32_t)row_shl<k>((int)bl), B_prev);
+					if constexpr (TSC) asm("" : "+s"(tpk));   /* (the same in every lane: the fold's v_bfi_b32 reads it from a scalar register) */
+					else asm("" : "+v"(tpk));
+					uint32_t Aup, Bup;
+					if constexpr (CBORD) { Aup = grp_up1c<G>(bxC, A_prev, lg); Bup = grp_up1c<G>(blC, B_prev, lg); }
+					else { Aup = grp_up1<G>((uint32_t)row_shl<k>((int)bx), A_prev); Bup = grp_up1<G>((uint32_t)row_shl<k>((int)bl), B_prev); }
 					const int jm1 = jm1_0 + k;
 					bool active = true;
 					if constexpr (masked) active = lg < nl && (unsigned)jm1 < (unsigned)il2;
@@ -1359,7 +1406,8 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 								uint32_t dlt = psub(best[c], cmax[c]);
 								asm("" : "+v"(dlt));                    /* keep hipcc from turning this into 2 cmp + 2 cndmask + perm */
 								const uint32_t g = pneg(dlt);           /* 0xffff where cmax > best */
-								bt[c] = vbfi(g, tpk, bt[c]);
+								if constexpr (TSC) bt[c] = vbfi_s(g, tpk, bt[c]);
+								else bt[c] = vbfi(g, tpk, bt[c]);
 								best[c] = pmax(best[c], cmax[c]);
 							}
 						}
