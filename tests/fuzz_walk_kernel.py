@@ -5,6 +5,7 @@ scoring (tie-heavy ones among them), related and unrelated pairs, site lists, od
 on and off -- every batch whole against the one-pass kernels (score, end cell, start state, ops) and a sample against the oracle.
 
     python3 tests/fuzz_walk_kernel.py [batches] [seed]
+    AT_FUZZ_WALK_PLANNED=1 python3 tests/fuzz_walk_kernel.py ...     # related pairs with planned paths (tests/test_planned_paths.py)
 
 Test infrastructure: the oracle is the checker.  (tests/fuzz_parity.py draws its shapes at random and meets these classes rarely.)
 """
@@ -23,6 +24,11 @@ def run(batches, seed, verbose=True):
     os.environ.setdefault("AT_PACKED_MIN_ROUNDS", "0")
     os.environ["AT_HOST_CHUNKS"] = "1"
     rng = random.Random(seed)
+    # AT_FUZZ_WALK_PLANNED=1: related pairs with a planned path (tests/test_planned_paths.py: a long vertical or horizontal run, a
+    # staircase of one-base gaps) instead of scattered edits.  Unset, no draw is added: the seeds keep their streams
+    planned = os.environ.get("AT_FUZZ_WALK_PLANNED") == "1"
+    if planned:
+        from test_planned_paths import planned_pair
     al = A.Aligner(0)
     seen = {}
     done = 0
@@ -45,6 +51,8 @@ def run(batches, seed, verbose=True):
         alpha = "ACGTN" if rng.random() < 0.15 else "ACGT"
 
         def mk(related):
+            if related and planned:
+                return planned_pair(rng, mode, l1, l2, alpha)
             a = "".join(rng.choice(alpha) for _ in range(l1))
             if not related:
                 return a, "".join(rng.choice(alpha) for _ in range(l2))

@@ -84,6 +84,25 @@ def test_fuzz_campaign_walk_kernel():
     assert n >= 120
 
 
+def test_fuzz_campaign_walk_kernel_planned_paths():
+    """The same campaign with AT_FUZZ_WALK_PLANNED=1, 40 batches: the related pairs hold a long vertical or horizontal run or a
+    staircase of one-base gaps (the generators of tests/test_planned_paths.py), so the walks leave their rounds' blocks sideways and
+    outrun them under random scorings, batch sizes and pieces."""
+    import fuzz_walk_kernel
+    names = ("AT_PACKED_MIN_ROUNDS", "AT_HOST_CHUNKS", "AT_FUZZ_WALK_PLANNED")
+    saved = {k: os.environ.get(k) for k in names}
+    os.environ["AT_FUZZ_WALK_PLANNED"] = "1"
+    try:
+        n = fuzz_walk_kernel.run(40, 43, verbose=False)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    assert n >= 40
+
+
 def test_fuzz_campaign_reached_every_kernel_family():
     """(runs behind the four campaigns of this module) what their batches ran on, by at_last_config"""
     if len(SEEN) == 0:
