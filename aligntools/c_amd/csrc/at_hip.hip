@@ -17,6 +17,7 @@
 #include "at_infix.hip.h"
 #include "at_scan.hip.h"
 #include "at_scanhits.hip.h"
+#include "at_localscan.hip.h"
 #include "at_pairhits.hip.h"
 #include "../../../include/aligntools_hip.h"
 
@@ -2801,6 +2802,396 @@ extern "C" int at_scan(at_handle *h,
 		if (rc || !cg) return rc;
 		return scan_cigars(h, nq, k, strands, rs, nt, maxq, bkey, bl4, out_target, out_score, out_end_i, out_end_j, flags, out_stats, out_ncigar,
 		                   out_cigar_off, out_cigar, cigar_cap);
+	});
+}
+
+/* ---- Smith-Waterman of reads against long targets (at_scan_local; at_localscan.hip.h) ---- */
+extern "C" int at_scan_local_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutoff, int32_t tile_cols, int m, int u, int o, int e,
+                                  int32_t *tile, int32_t *overlap, int64_t *ntiles, int64_t *nfull)
+{
+	at::LocalScanPlan sp;
+	const int rc = at::localscan_plan(len1, len2, use_cutoff, cutoff, tile_cols, m, u, o, e, &sp);
+	if (rc == AT_ERR_ARG)
+		return fail(nullptr, AT_ERR_ARG, "at_scan_local_plan: a negative length, or tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)",
+		            tile_cols, at::kLocalScanDefaultTile);
+	if (rc != AT_OK)
+		return fail(nullptr, AT_ERR_DOMAIN, "at_scan_local_plan: needs m >= 1, o <= -1, e <= -1 and a query of 1 .. %d bases with max(m, u) * length < 2^%d",
+		            at::kLocalScanMaxQuery, at::kLocalScanScoreBits);
+	if (tile) *tile = sp.tile;
+	if (overlap) *overlap = sp.overlap;
+	if (ntiles) *ntiles = sp.ntiles;
+	if (nfull) *nfull = sp.nfull;
+	return AT_OK;
+}
+
+extern "C" int64_t at_scan_local_window(int32_t end_i, int64_t end_j, int32_t score, int m, int u, int o, int e)
+{
+	if (o == 0 || e == 0) return 0;
+	return at::localscan_window_start(end_j, end_i, score, m, u, o, e);
+}
+
+/* the lists of at_scan_local: the blocks of search_lists with the targets in caller order.  A block's pairs go in RUNS of at most
+ * `chunk` pairs whose key slots stay until every tile of the run is folded; a run's tiles go in two passes (the tiles of the full
+ * shape, a uniform batch, and the shorter ones at the targets' ends) and each pass in SLICES of at most `chunk` tile pairs:
+ * descriptors, the batch entry's sweep, fold.  Behind the last slice the run's slots are unpacked and merged.  The lists stay in
+ * h->d_str behind the call. */
+static int localscan_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64_t nt, const int32_t *t_len, const ReadSet &rs,
+                           int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile, int32_t *out_target, int32_t *out_score,
+                           int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state, int32_t *out_strand, int32_t *out_nhits,
+                           size_t *list_bkey, size_t *list_b4)
+{
+	const int enc = strands != AT_STRAND_FWD, two = strands == AT_STRAND_BOTH;
+	const int64_t nv = nq << two;
+	std::vector<int> qs((size_t)nq), qperm((size_t)nv), tperm((size_t)nt);
+	for (int64_t q = 0; q < nq; ++q) qs[(size_t)q] = (int)q;
+	for (int64_t t = 0; t < nt; ++t) tperm[(size_t)t] = (int)t;
+	std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
+	for (int64_t q = 0; q < nq; ++q) {
+		const int c = qs[(size_t)q];
+		if (two) { qperm[(size_t)(2 * q)] = c << 1; qperm[(size_t)(2 * q + 1)] = (c << 1) | 1; }
+		else qperm[(size_t)q] = enc ? (c << 1) | 1 : c;
+	}
+	struct Block { int qa, nqb; int32_t l1; };
+	std::vector<Block> blocks;
+	int64_t most = 0;
+	for (int64_t a = 0, b; a < nq; a = b) {
+		const int32_t L = q_len[qs[(size_t)a]];
+		for (b = a; b < nq && q_len[qs[(size_t)b]] == L; ++b) {}
+		blocks.push_back({(int)(a << two), (int)((b - a) << two), L});
+		most = std::max<int64_t>(most, ((b - a) << two) * nt);
+	}
+	int32_t maxt = 0;
+	for (int64_t t = 0; t < nt; ++t) maxt = std::max(maxt, t_len[t]);
+	/* a slice holds tile pairs: a run has at least as many tiles as pairs, so the bound of the largest block's tiles is not known here */
+	int64_t chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
+	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, 1LL << 28));
+	{
+		const int64_t most_tiles = most * std::max<int64_t>(1, at::localscan_tiles(maxt, tile));   /* (an upper bound: some are not swept) */
+		chunk = std::min<int64_t>(chunk, std::max<int64_t>(most_tiles, 1));
+	}
+	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	const size_t b8 = al((size_t)chunk * 8), b4 = al((size_t)chunk * 4), bq = al((size_t)nv * 4), bt = al((size_t)nt * 4), bg = al(((size_t)nt + 1) * 8);
+	const size_t nl = (size_t)nq * (size_t)k, bkey = al(nl * 8), bl4 = al(nl * 4);
+	int rc = grow(h, &h->d_desc, &h->desc_bytes, 5 * b8 + 2 * b4 + 2 * bg + bq + bt);
+	if (rc) return rc;
+	rc = grow(h, &h->d_out, &h->out_bytes, 8 * b4);
+	if (rc) return rc;
+	const size_t lbytes = bkey + 3 * bl4 + 256;
+	rc = grow(h, &h->d_str, &h->str_bytes, lbytes);
+	if (rc) return rc;
+	char *dd = (char *)h->d_desc, *dr = (char *)h->d_out, *dl = (char *)h->d_str;
+	int64_t *d_woff1 = (int64_t *)dd, *d_woff2 = (int64_t *)(dd + b8);
+	long long *d_s0 = (long long *)(dd + 2 * b8), *d_slot = (long long *)(dd + 3 * b8);
+	unsigned long long *d_pkey = (unsigned long long *)(dd + 4 * b8);
+	int32_t *d_len1 = (int32_t *)(dd + 5 * b8), *d_len2 = (int32_t *)(dd + 5 * b8 + b4);
+	long long *d_tpre[2] = {(long long *)(dd + 5 * b8 + 2 * b4), (long long *)(dd + 5 * b8 + 2 * b4 + bg)};
+	int *d_qperm = (int *)(dd + 5 * b8 + 2 * b4 + 2 * bg), *d_tperm = (int *)(dd + 5 * b8 + 2 * b4 + 2 * bg + bq);
+	int32_t *d_r[8];
+	for (int x = 0; x < 8; ++x) d_r[x] = (int32_t *)(dr + (size_t)x * b4);
+	unsigned long long *d_key = (unsigned long long *)dl;
+	int *d_lei = (int *)(dl + bkey), *d_lej = (int *)(dl + bkey + bl4), *d_lst = (int *)(dl + bkey + 2 * bl4), *d_bad = (int *)(dl + bkey + 3 * bl4);
+	hipStream_t s = h->stream;
+	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nv * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_tperm, tperm.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemsetAsync(dl, 0, lbytes, s));
+	std::string cfg0;
+	int64_t nslices = 0, tiles_all = 0, ov_most = 0;
+	struct Ev { hipEvent_t e[2] = {nullptr, nullptr}; ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
+	for (hipEvent_t &x : ev.e) HIP_TRY(h, hipEventCreate(&x));
+	HIP_TRY(h, hipEventRecord(ev.e[0], s));
+	std::vector<long long> tpre[2];
+	for (auto &v : tpre) v.assign((size_t)nt + 1, 0);
+	for (const Block &B : blocks) {
+		/* the overlap depends on the query length: the block's prefix arrays of full and of shorter tiles per target */
+		const int64_t ov = at::localscan_overlap(B.l1, use_cutoff, cutoff, h->m, h->u, h->o, h->e);
+		{
+			/* a tile is a pair of the batch entry: its exact-score bound (align_device), said here with the tile's numbers */
+			long long maxabs = 1;
+			for (int v : {h->m, h->u, h->o, h->e, h->j}) maxabs = std::max<long long>(maxabs, std::llabs((long long)v));
+			if (maxabs * ((long long)B.l1 + tile + ov + 2) >= (1LL << 24))
+				return fail(h, AT_ERR_RANGE, "at_scan_local: a tile of %d rows x %d + %lld columns may leave the exact score range: max|param| = %lld", B.l1,
+				            tile, (long long)ov, maxabs);
+		}
+		ov_most = std::max(ov_most, ov);
+		int32_t rag_most = 0;
+		for (int64_t t = 0; t < nt; ++t) {
+			/* (the swept tiles: the repeats of tile 0 are left out) */
+			const int64_t n = at::localscan_swept(t_len[t], tile, ov), nf = at::localscan_swept_full(t_len[t], tile, ov);
+			const int64_t d = at::localscan_dropped(t_len[t], tile, ov);
+			tpre[0][(size_t)t + 1] = tpre[0][(size_t)t] + nf;
+			tpre[1][(size_t)t + 1] = tpre[1][(size_t)t] + (n - nf);
+			for (int64_t k2 = nf; k2 < n; ++k2) {
+				const int64_t x = at::localscan_swept_tile(k2, d);
+				rag_most = std::max<int32_t>(rag_most, (int32_t)(at::localscan_tile_end(x, tile, ov, t_len[t]) - at::localscan_tile_start(x, tile, ov)));
+			}
+		}
+		tiles_all += (tpre[0][(size_t)nt] + tpre[1][(size_t)nt]) * B.nqb;
+		/* (the copies read the vectors when they run: the stream is drained before the next block rewrites them) */
+		for (int x = 0; x < 2; ++x) HIP_TRY(h, hipMemcpyAsync(d_tpre[x], tpre[x].data(), ((size_t)nt + 1) * 8, hipMemcpyHostToDevice, s));
+		HIP_TRY(h, hipStreamSynchronize(s));
+		const int64_t bp = (int64_t)B.nqb * nt;
+		for (int64_t p0 = 0; p0 < bp; p0 += chunk) {
+			const int64_t n = std::min(chunk, bp - p0);
+			at::LocalScanArgs sa;
+			memset(&sa, 0, sizeof sa);
+			sa.cap = chunk; sa.p0 = p0; sa.npairs = n; sa.ntb = nt;
+			sa.qa = B.qa; sa.nq = (int)nq; sa.enc = enc; sa.nrev0 = (int)(nq + nt); sa.bpw = rs.bits == 2 ? 16 : 4; sa.qperm = d_qperm;
+			sa.swoff = (const long long *)rs.d_swoff; sa.slen = rs.d_len; sa.tile = tile; sa.overlap = ov;
+			sa.woff1 = (long long *)d_woff1; sa.woff2 = (long long *)d_woff2; sa.len1 = d_len1; sa.len2 = d_len2; sa.s0 = d_s0; sa.slot = d_slot;
+			sa.score = d_r[0]; sa.end_i = d_r[1]; sa.end_j = d_r[2];
+			sa.key = d_pkey; sa.bad = d_bad;
+			sa.o_score = d_r[4]; sa.o_end_i = d_r[5]; sa.o_end_j = d_r[6]; sa.o_state = d_r[7];
+			HIP_TRY(h, at_localscan_init_launch(&sa, h->ncu, s));
+			for (int pass = 0; pass < 2; ++pass) {
+				const long long tall = tpre[pass][(size_t)nt];
+				if (tall == 0) continue;
+				auto items_before = [&](int64_t x) { return (long long)(x / nt) * tall + tpre[pass][(size_t)(x % nt)]; };
+				const long long ya = items_before(p0), yb = items_before(p0 + n);
+				sa.ragged = pass; sa.tall = tall; sa.tpre = d_tpre[pass];
+				for (long long y = ya; y < yb; y += chunk) {
+					sa.y0 = y; sa.nitems = std::min<long long>(chunk, yb - y);
+					HIP_TRY(h, at_localscan_desc_launch(&sa, h->ncu, s));
+					rc = align_device(h, AT_MODE_LOCAL, sa.nitems, rs.d_words, rs.bits, d_woff1, d_len1, d_woff2, d_len2, B.l1,
+					                  pass ? rag_most : (int32_t)(tile + ov), pass ? 0 : 1, 0, d_r[0], d_r[1], d_r[2], d_r[3], nullptr, nullptr, nullptr, s, 0, 0);
+					if (rc) { (void)hipStreamSynchronize(s); return rc; }
+					if (nslices == 0) cfg0 = h->cfg;
+					HIP_TRY(h, at_localscan_fold_launch(&sa, h->ncu, s));
+					++nslices;
+				}
+			}
+			HIP_TRY(h, at_localscan_unpack_launch(&sa, h->ncu, s));
+			at::SearchMergeArgs ma;
+			memset(&ma, 0, sizeof ma);
+			ma.s0 = p0; ma.n = n; ma.ntb = nt; ma.qa = B.qa; ma.ta = 0;
+			ma.enc = enc; ma.two = two;
+			ma.nqs = (int)((p0 + n - 1) / (nt << two) - p0 / (nt << two) + 1);
+			ma.qperm = d_qperm; ma.tperm = d_tperm;
+			ma.score = d_r[4]; ma.end_i = d_r[5]; ma.end_j = d_r[6]; ma.state = d_r[7];
+			ma.k = k; ma.is_edit = 0; ma.use_cutoff = use_cutoff ? 1 : 0; ma.cutoff = cutoff;
+			ma.lkey = d_key; ma.lei = d_lei; ma.lej = d_lej; ma.lst = d_lst; ma.bad = d_bad;
+			HIP_TRY(h, at_search_merge_launch(&ma, s));
+		}
+	}
+	HIP_TRY(h, hipEventRecord(ev.e[1], s));
+	std::vector<char> hl(lbytes);
+	HIP_TRY(h, hipMemcpyAsync(hl.data(), dl, lbytes, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipStreamSynchronize(s));
+	float sweep_ms = 0.f;
+	HIP_TRY(h, hipEventElapsedTime(&sweep_ms, ev.e[0], ev.e[1]));
+	int bad = 0;
+	memcpy(&bad, hl.data() + bkey + 3 * bl4, 4);
+	if (bad) return fail(h, AT_ERR_DOMAIN, "at_scan_local: a pair outside the domain on which the reference is defined");
+	const unsigned long long *hk = (const unsigned long long *)hl.data();
+	const int32_t *hei = (const int32_t *)(hl.data() + bkey), *hej = (const int32_t *)(hl.data() + bkey + bl4), *hst = (const int32_t *)(hl.data() + bkey + 2 * bl4);
+	for (int64_t q = 0; q < nq; ++q) {
+		int nh = 0;
+		for (int j = 0; j < k; ++j) {
+			const size_t e = (size_t)q * k + j;
+			if (!hk[e]) break;
+			const uint32_t low = ~(uint32_t)hk[e];
+			out_target[e] = (int32_t)(low >> enc);
+			if (out_strand) out_strand[e] = enc ? (int32_t)(low & 1u) : 0;
+			out_score[e] = (int32_t)((uint32_t)(hk[e] >> 32) ^ 0x80000000u);
+			out_end_i[e] = hei[e]; out_end_j[e] = hej[e]; out_state[e] = hst[e];
+			++nh;
+		}
+		out_nhits[q] = nh;
+	}
+	/* (the sweep phase's device time as scan_lists reports it: tools/local_scan_rate.py; at most 360 bytes, which localscan_cigars keeps whole) */
+	snprintf(h->cfg, sizeof h->cfg, "local-scan: tile=%d overlap<=%lld tiles=%lld k=%d strands=%s, %lld blocks, %lld slices; %.200s sweep=%.3fms", tile,
+	         (long long)ov_most, (long long)tiles_all, k, scan_strands_text(strands), (long long)blocks.size(), (long long)nslices, cfg0.c_str(), (double)sweep_ms);
+	*list_bkey = bkey; *list_b4 = bl4;
+	return AT_OK;
+}
+
+/* the alignments of the hits: every USED list entry as a window pair (query, target columns (ws, j*]) through the batch entry with
+ * tracebacks and the CIGAR kernels (at_localscan.hip.h), in pieces of at most 2^20 hits or 1 GB of op slots (3.13's bounds) and no
+ * more hits than a slice has pairs (AT_ALLPAIRS_CHUNK: the tests' 1 and 7 make pieces of 1 and 7 hits).  Unused entries keep what the entry gave them: 0 runs, a row of
+ * -1 and no room in out_cigar */
+static int localscan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadSet &rs, int64_t nt, int32_t maxq, size_t bkey, size_t bl4,
+                            const int32_t *out_target, const int32_t *out_score, const int32_t *out_end_i, const int32_t *out_end_j, int flags,
+                            int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap)
+{
+	const int enc = strands != AT_STRAND_FWD;
+	const int64_t nlist = nq * k;
+	std::vector<long long> used;
+	std::vector<int32_t> wlen;
+	for (int64_t e = 0; e < nlist; ++e) {
+		if (out_target[e] < 0) continue;
+		used.push_back(e);
+		wlen.push_back((int32_t)(out_end_j[e] - at::localscan_window_start(out_end_j[e], out_end_i[e], out_score[e], h->m, h->u, h->o, h->e)));
+	}
+	const int64_t nused = (int64_t)used.size();
+	const int64_t piece_hits = std::max<long long>(1, std::min<long long>(env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20), 1LL << 20));
+	const int64_t piece_ops = 1LL << 30;
+	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	hipStream_t s = h->stream;
+	char *dl = (char *)h->d_str;
+	const std::string cfg0 = h->cfg;
+	std::string cfg1;
+	int64_t words_total = 0, npieces = 0;   /* CIGAR words of the hits so far: the next piece's place in out_cigar */
+	bool fits = true;                        /* every entry so far ends within the caller's capacity */
+	int64_t next_entry = 0;                  /* out_cigar_off is complete up to here */
+	for (int64_t a0 = 0; a0 < nused; ) {
+		int64_t n = 0, ops_bytes = 0;
+		int32_t max2 = 1;
+		std::vector<int64_t> slot;
+		while (a0 + n < nused && n < piece_hits) {
+			const int64_t need = (int64_t)maxq + wlen[(size_t)(a0 + n)];
+			if (n > 0 && ops_bytes + need > piece_ops) break;
+			slot.push_back(ops_bytes);
+			ops_bytes += need;
+			max2 = std::max(max2, wlen[(size_t)(a0 + n)]);
+			++n;
+		}
+		const size_t b8 = al((size_t)(n + 1) * 8), b4 = al((size_t)n * 4), bst = al((size_t)n * 32);
+		const int64_t dcap = std::min<int64_t>(std::max<int64_t>(cigar_cap - words_total, 0), ops_bytes);   /* (a list has no more runs than ops) */
+		int rc = grow(h, &h->d_out, &h->out_bytes, 4 * b8 + 8 * b4);
+		if (rc) return rc;
+		rc = grow(h, &h->d_order, &h->order_bytes, (size_t)ops_bytes + 256);
+		if (rc) return rc;
+		rc = grow(h, &h->d_cg, &h->cg_bytes, b4 + bst + b8 + al((size_t)dcap * 4) + 256);
+		if (rc) return rc;
+		char *dw = (char *)h->d_out, *dc = (char *)h->d_cg;
+		int64_t *d_woff1 = (int64_t *)dw, *d_woff2 = (int64_t *)(dw + b8), *d_ops_off = (int64_t *)(dw + 2 * b8);
+		long long *d_eidx = (long long *)(dw + 3 * b8);
+		int32_t *d4[8];
+		for (int x = 0; x < 8; ++x) d4[x] = (int32_t *)(dw + 4 * b8 + (size_t)x * b4);
+		int32_t *d_len1 = d4[0], *d_len2 = d4[1], *d_ws = d4[2], *d_sc = d4[3], *d_ei = d4[4], *d_ej = d4[5], *d_st = d4[6], *d_nops = d4[7];
+		int32_t *d_ncigar = (int32_t *)dc, *d_stats = (int32_t *)(dc + b4);
+		int64_t *d_coff = (int64_t *)(dc + b4 + bst);
+		uint32_t *d_cigar = (uint32_t *)(dc + b4 + bst + b8);
+		int *d_bad = (int *)(dc + b4 + bst + b8 + al((size_t)dcap * 4));
+		uint8_t *d_ops = (uint8_t *)h->d_order;
+		HIP_TRY(h, hipMemcpyAsync(d_ops_off, slot.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+		HIP_TRY(h, hipMemcpyAsync(d_eidx, used.data() + a0, (size_t)n * 8, hipMemcpyHostToDevice, s));
+		HIP_TRY(h, hipMemsetAsync(d_bad, 0, 4, s));
+		at::LocalScanWindowArgs wa;
+		memset(&wa, 0, sizeof wa);
+		wa.n = n; wa.nlist = nlist; wa.eidx = d_eidx; wa.k = k; wa.nq = (int)nq; wa.enc = enc; wa.nrev0 = (int)(nq + nt); wa.bpw = rs.bits == 2 ? 16 : 4;
+		wa.m = h->m; wa.u = h->u; wa.o = h->o; wa.e = h->e;
+		wa.lkey = (const unsigned long long *)dl; wa.lei = (const int *)(dl + bkey); wa.lej = (const int *)(dl + bkey + bl4);
+		wa.swoff = (const long long *)rs.d_swoff; wa.slen = rs.d_len;
+		wa.woff1 = (long long *)d_woff1; wa.woff2 = (long long *)d_woff2; wa.len1 = d_len1; wa.len2 = d_len2; wa.ws = d_ws;
+		wa.w_score = d_sc; wa.w_end_i = d_ei; wa.w_end_j = d_ej; wa.ncigar = d_ncigar; wa.stats = d_stats; wa.bad = d_bad;
+		HIP_TRY(h, at_localscan_window_launch(&wa, h->ncu, s));
+		rc = align_device(h, AT_MODE_LOCAL, n, rs.d_words, rs.bits, d_woff1, d_len1, d_woff2, d_len2, maxq, max2, 0, 1, d_sc, d_ei, d_ej, d_st,
+		                  d_ops, d_ops_off, d_nops, s, 0, 0);
+		if (rc) { (void)hipStreamSynchronize(s); return rc; }
+		if (cfg1.empty()) cfg1 = h->cfg;
+		rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_ops_off, d_nops, flags, d_ncigar, d_stats, d_coff,
+		                           d_cigar, dcap, s);
+		if (rc) { (void)hipStreamSynchronize(s); return rc; }
+		HIP_TRY(h, at_localscan_check_launch(&wa, h->ncu, s));
+		int bad = 0;
+		std::vector<int32_t> hnc((size_t)n), hst((size_t)n * 8);
+		std::vector<int64_t> hco((size_t)n + 1);
+		HIP_TRY(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(h, hipMemcpyAsync(hnc.data(), d_ncigar, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(h, hipMemcpyAsync(hst.data(), d_stats, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+		HIP_TRY(h, hipMemcpyAsync(hco.data(), d_coff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(h, hipStreamSynchronize(s));
+		if (bad) return fail(h, AT_ERR_RANGE, "at_scan_local: a hit's window does not reproduce its score and end cell (target columns (ws, j*] of at most %d)", max2);
+		/* the piece's words that end within the caller's capacity: a prefix of the device buffer, behind the pieces before it */
+		int64_t fit = 0;
+		for (int64_t x = 0; x < n; ++x) {
+			const int64_t e = used[(size_t)(a0 + x)];
+			for (; next_entry <= e; ++next_entry) out_cigar_off[next_entry] = words_total + hco[(size_t)x];
+			out_ncigar[e] = hnc[(size_t)x];
+			memcpy(out_stats + e * 8, hst.data() + x * 8, 32);
+			if (fits && words_total + hco[(size_t)x + 1] <= cigar_cap) fit = hco[(size_t)x + 1]; else fits = false;
+		}
+		if (fit > 0) {
+			HIP_TRY(h, hipMemcpyAsync(out_cigar + words_total, d_cigar, (size_t)fit * 4, hipMemcpyDeviceToHost, s));
+			HIP_TRY(h, hipStreamSynchronize(s));
+		}
+		words_total += hco[(size_t)n];
+		a0 += n;
+		++npieces;
+	}
+	for (; next_entry <= nlist; ++next_entry) out_cigar_off[next_entry] = words_total;
+	snprintf(h->cfg, sizeof h->cfg, "%.360s; windows: %.180s, %lld pieces, cigars: %d lanes/pair", cfg0.c_str(), cfg1.c_str(), (long long)npieces, h->last_cigar_lanes);
+	return AT_OK;
+}
+
+extern "C" int at_scan_local(at_handle *h,
+                             int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+                             int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+                             int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile_cols, int flags,
+                             int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
+                             int32_t *out_state, int32_t *out_strand, int32_t *out_nhits,
+                             int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
+                             uint32_t *out_cigar, int64_t cigar_cap)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_scan_local: NULL handle");
+	if (nq < 0 || nt < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "at_scan_local: negative size");
+	if (k < 1 || k > 64) return fail(h, AT_ERR_ARG, "at_scan_local: k = %d outside 1..64", k);
+	if (strands < AT_STRAND_FWD || strands > AT_STRAND_BOTH) return fail(h, AT_ERR_ARG, "at_scan_local: strands = %d outside 1..3", strands);
+	if (tile_cols < 0 || (tile_cols & 15))
+		return fail(h, AT_ERR_ARG, "at_scan_local: tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)", tile_cols, at::kLocalScanDefaultTile);
+	if (flags & ~AT_CIGAR_M) return fail(h, AT_ERR_ARG, "at_scan_local: flags = %d (AT_CIGAR_M or 0)", flags);
+	const bool rev = strands != AT_STRAND_FWD;
+	const bool cg = out_stats || out_ncigar || out_cigar_off || out_cigar;
+	if (cg && (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)))
+		return fail(h, AT_ERR_ARG, "at_scan_local: the CIGAR outputs are either all NULL or all given");
+	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "at_scan_local: %lld queries + %lld targets: at most 2^31 - 1 reads", (long long)nq, (long long)nt);
+	if (rev && (nt >= (1LL << 30) || 2 * nq + nt >= (1LL << 31)))
+		return fail(h, AT_ERR_ARG, "at_scan_local: %lld queries, %lld targets: a reverse strand needs nt < 2^30 and 2 nq + nt < 2^31", (long long)nq, (long long)nt);
+	if (h->comm) return fail(h, AT_ERR_DOMAIN, "at_scan_local: one GPU only (this handle belongs to a multi-process job)");
+	if (at::localscan_scoring_ok(h->m, h->o, h->e) != AT_OK)
+		return fail(h, AT_ERR_DOMAIN, "at_scan_local needs m >= 1, o <= -1 and e <= -1: m = %d, o = %d, e = %d", h->m, h->o, h->e);
+	if (nq == 0) return AT_OK;
+	if (!q_blob || !q_off || !q_len || !out_target || !out_score || !out_end_i || !out_end_j || !out_state || !out_nhits ||
+	    (rev && !out_strand) || (nt > 0 && (!t_blob || !t_off || !t_len)))
+		return fail(h, AT_ERR_ARG, "at_scan_local: NULL argument");
+	int32_t maxq = 0;
+	for (int64_t q = 0; q < nq; ++q) {
+		if (q_len[q] < 0 || q_off[q] < 0) return fail(h, AT_ERR_ARG, "query %lld: negative length or offset", (long long)q);
+		if (q_len[q] < 1) return fail(h, AT_ERR_DOMAIN, "query %lld: empty", (long long)q);
+		if (at::localscan_query_ok(q_len[q], h->m, h->u) != AT_OK)
+			return fail(h, AT_ERR_DOMAIN, "at_scan_local: query %lld has %d bases: at most %d, and max(m, u) * length < 2^%d", (long long)q, q_len[q],
+			            at::kLocalScanMaxQuery, at::kLocalScanScoreBits);
+		maxq = std::max(maxq, q_len[q]);
+	}
+	for (int64_t t = 0; t < nt; ++t) {
+		if (t_len[t] < 0 || t_off[t] < 0) return fail(h, AT_ERR_ARG, "target %lld: negative length or offset", (long long)t);
+		if (t_len[t] < 1) return fail(h, AT_ERR_DOMAIN, "target %lld: empty", (long long)t);
+	}
+	const int32_t tile = tile_cols > 0 ? tile_cols : at::kLocalScanDefaultTile;
+	return guarded(h, "at_scan_local", [&]() -> int {
+		for (int64_t e = 0; e < nq * k; ++e) { out_target[e] = -1; out_score[e] = 0; out_end_i[e] = 0; out_end_j[e] = 0; out_state[e] = 0; }
+		if (out_strand) for (int64_t e = 0; e < nq * k; ++e) out_strand[e] = -1;
+		for (int64_t q = 0; q < nq; ++q) out_nhits[q] = 0;
+		if (cg) {
+			for (int64_t e = 0; e < nq * k; ++e) { out_ncigar[e] = 0; for (int x = 0; x < 8; ++x) out_stats[e * 8 + x] = -1; }
+			for (int64_t e = 0; e <= nq * k; ++e) out_cigar_off[e] = 0;
+		}
+		if (nt == 0) {
+			snprintf(h->cfg, sizeof h->cfg, "local-scan: tile=%d overlap<=0 tiles=0 k=%d strands=%s, 0 blocks, 0 slices; ", tile, k, scan_strands_text(strands));
+			return (int)AT_OK;
+		}
+		int64_t bytes = 0;
+		for (int64_t q = 0; q < nq; ++q) bytes += q_len[q];
+		for (int64_t t = 0; t < nt; ++t) bytes += t_len[t];
+		std::vector<uint8_t> blob((size_t)bytes + 32);
+		std::vector<int64_t> off((size_t)(nq + nt));
+		std::vector<int32_t> len((size_t)(nq + nt));
+		int64_t at = 0;
+		for (int64_t r = 0; r < nq + nt; ++r) {
+			const bool isq = r < nq;
+			const int32_t l = isq ? q_len[r] : t_len[r - nq];
+			if (l) memcpy(blob.data() + at, isq ? q_blob + q_off[r] : t_blob + t_off[r - nq], (size_t)l);
+			off[(size_t)r] = at; len[(size_t)r] = l; at += l;
+		}
+		ReadSet rs;
+		int rc = upload_reads(h, AT_MODE_LOCAL, nq + nt, blob.data(), off.data(), len.data(), &rs, rev ? nq : 0);
+		if (rc) return rc;
+		size_t bkey = 0, bl4 = 0;
+		rc = localscan_lists(h, nq, q_len, nt, t_len, rs, k, use_cutoff, cutoff, strands, tile, out_target, out_score, out_end_i, out_end_j, out_state,
+		                     out_strand, out_nhits, &bkey, &bl4);
+		if (rc || !cg) return rc;
+		return localscan_cigars(h, nq, k, strands, rs, nt, maxq, bkey, bl4, out_target, out_score, out_end_i, out_end_j, flags, out_stats, out_ncigar,
+		                        out_cigar_off, out_cigar, cigar_cap);
 	});
 }
 

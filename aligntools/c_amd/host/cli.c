@@ -160,6 +160,10 @@ static int main_single(int cmd, int argc, char *argv[])
  *     --scan         (edit -u 1 --infix --queries, with --score-only or --paf) reads against LONG targets (at_scan): the hits of the
  *                    --queries form with no bound on the target length; --score-only prints their hit lines, --paf their PAF lines
  *                    (target start and end absolute, cg:Z the =/X CIGAR).  Not with --all-vs-all, --gpus N > 1.
+ *     --long-targets (local --queries, with --score-only or --paf) Smith-Waterman of reads against LONG targets (at_scan_local): the
+ *                    hits of `batch local --queries` with no bound on the target length; --score-only prints their hit lines,
+ *                    --paf their PAF lines.  --best, --both-strands and --min-score as with --queries.  Queries of up to 1 024
+ *                    bases; -m >= 1, -o <= -1, -e <= -1.  Not with --all-vs-all, --gpus N > 1, --scan, --infix, --keep.
  *     --all-hits D   (with --scan) EVERY occurrence of every read with at most D edits (at_scan_hits) instead of the best K hits:
  *                    --score-only prints "query\ttarget\tedit_distance=d\tend=J" per hit (J the absolute end column; "\t+" / "\t-"
  *                    with --both-strands), --paf the PAF line of --scan.  --min-sep S keeps an occurrence only if no better one
@@ -173,7 +177,7 @@ static int main_single(int cmd, int argc, char *argv[])
  * thread -- which also pays the HIP start-up, in the shadow of the first chunks' parsing -- sends each chunk to the GPU
  * and writes its results with one fwrite.  Memory is bounded by the chunks in flight, whatever the size of the file;
  * --all-vs-all keeps the read set and streams slices of the triangle instead (at_align_allpairs_stream). */
-typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments, infix, scan; int all_hits, max_dist, sep_set, min_sep; int keep_on, keep; } batch_flags;
+typedef struct { int score_only, all_vs_all, gpus, min_on, min_score; const char *queries; int best, best_set, both, paf, alignments, infix, scan; int all_hits, max_dist, sep_set, min_sep; int keep_on, keep; int long_targets; } batch_flags;
 static int g_edit_alignments;   /* --alignments: every handle of this process delivers edit alignments (set before any handle exists) */
 static int g_edit_infix;        /* --infix: every handle of this process is in edit infix mode (at_set_edit_infix; set likewise) */
 
@@ -815,7 +819,8 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 }
 
 /* ---- --scan (edit -u 1 --infix --queries): reads against long targets, the best K hits of each query (at_scan) ----
- * --score-only prints the hit lines of the --queries form, --paf its PAF lines; the CIGARs come with the hits, from the same call. */
+ * --score-only prints the hit lines of the --queries form, --paf its PAF lines; the CIGARs come with the hits, from the same call.
+ * --long-targets (local --queries) is the same form over at_scan_local: scores instead of distances, --min-score as its cutoff. */
 static int batch_scan(opt_t *opt, const batch_flags *bf, const char *qfile, const char *tfile)
 {
 	at_reader *rq = at_reader_open(qfile), *rt;
@@ -856,8 +861,13 @@ static int batch_scan(opt_t *opt, const batch_flags *bf, const char *qfile, cons
 	trace("scan: records read, queries", nq);
 	for (pass = 0; pass < 2; ++pass) {       /* a second call if the hits have more runs than the first guess */
 		if (bf->paf) { free(cg); cg = (uint32_t *)at_xmalloc((size_t)cap * 4); }
-		rc = at_scan(h, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, 0, 0, bf->both ? AT_STRAND_BOTH : AT_STRAND_FWD, 0, 0,
-		             tgt, sc, ei, ej, st, sd, nh, stats, ncg, cgoff, cg, cap);
+		if (bf->long_targets) {
+			rc = at_scan_local(h, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, bf->min_on, bf->min_score,
+			                   bf->both ? AT_STRAND_BOTH : AT_STRAND_FWD, 0, 0, tgt, sc, ei, ej, st, sd, nh, stats, ncg, cgoff, cg, cap);
+		} else {
+			rc = at_scan(h, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, 0, 0, bf->both ? AT_STRAND_BOTH : AT_STRAND_FWD, 0, 0,
+			             tgt, sc, ei, ej, st, sd, nh, stats, ncg, cgoff, cg, cap);
+		}
 		if (rc != AT_OK) die("%s", at_last_error(h));
 		if (!bf->paf || cgoff[n] <= cap) break;
 		cap = cgoff[n];
@@ -868,10 +878,10 @@ static int batch_scan(opt_t *opt, const batch_flags *bf, const char *qfile, cons
 			const int64_t e = q * kb + j;
 			const char strand = sd[e] == 1 ? '-' : '+';
 			if (bf->paf)
-				tb_paf(&out, c.names + c.name_off[q], qlen[q], strand, c.names + c.name_off[nq + tgt[e]], tlen[tgt[e]], -sc[e], ei[e], ej[e],
-				       stats + 8 * e, cg + cgoff[e], ncg[e]);
+				tb_paf(&out, c.names + c.name_off[q], qlen[q], strand, c.names + c.name_off[nq + tgt[e]], tlen[tgt[e]],
+				       bf->long_targets ? sc[e] : -sc[e], ei[e], ej[e], stats + 8 * e, cg + cgoff[e], ncg[e]);
 			else
-				tb_pair_strand(&out, c.names + c.name_off[q], c.names + c.name_off[nq + tgt[e]], sc[e], 1, bf->both ? strand : 0, NULL, NULL, 0);
+				tb_pair_strand(&out, c.names + c.name_off[q], c.names + c.name_off[nq + tgt[e]], sc[e], !bf->long_targets, bf->both ? strand : 0, NULL, NULL, 0);
 		}
 		if (out.l > ((size_t)8 << 20)) tb_flush(&out);
 	}
@@ -1014,10 +1024,10 @@ static int main_batch(int argc, char *argv[], char *argv0)
 {
 	int cmd = -1, k, n = 0;
 	opt_t *opt = init_opt();
-	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, AT_SCAN_SEP_READ, 0, 0};
+	batch_flags bf = {0, 0, 1, 0, 0, NULL, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, AT_SCAN_SEP_READ, 0, 0, 0};
 	char **av = (char **)at_xmalloc((size_t)(argc + 1) * sizeof(char *));
 	const char *usage_line = "Usage:   alignTools batch <global|local|fit|overlap|edit> [options] [--score-only] [--all-vs-all] [--min-score T] [--keep T] [--gpus N] [--paf] [--alignments] [--infix] [--scan] <pairs.fa>\n"
-	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] [--infix] [--scan] [--all-hits D] [--min-sep S] <targets.fa>\n";
+	                         "         alignTools batch <global|local|fit|overlap|edit> [options] --queries <queries.fa> [--best K] [--both-strands] [--min-score T] [--score-only] [--paf] [--alignments] [--infix] [--scan] [--all-hits D] [--min-sep S] [--long-targets] <targets.fa>\n";
 	/* the long flags of the extension are taken out before getopt sees the reference's short options */
 	for (k = 0; k < argc; ++k) {
 		if (strcmp(argv[k], "--score-only") == 0) bf.score_only = 1;
@@ -1032,6 +1042,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 		else if (strcmp(argv[k], "--alignments") == 0) bf.alignments = 1;
 		else if (strcmp(argv[k], "--infix") == 0) bf.infix = 1;
 		else if (strcmp(argv[k], "--scan") == 0) bf.scan = 1;
+		else if (strcmp(argv[k], "--long-targets") == 0) bf.long_targets = 1;
 		else if (strcmp(argv[k], "--all-hits") == 0 && k + 1 < argc) { bf.all_hits = 1; bf.max_dist = atoi(argv[++k]); }
 		else if (strcmp(argv[k], "--min-sep") == 0 && k + 1 < argc) { bf.sep_set = 1; bf.min_sep = atoi(argv[++k]); }
 		else av[n++] = argv[k];
@@ -1043,7 +1054,13 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	/* --queries: refused with what it cannot go with, before any GPU call */
 	{
 		const char *why = NULL;
-		if (bf.keep_on && bf.queries) why = "--keep does not go with --queries (it keeps pairs of --all-vs-all)";
+		if (bf.long_targets && cmd != C_LOCAL) why = "--long-targets goes with local";
+		else if (bf.long_targets && !bf.queries) why = "--long-targets goes with --queries (reads against long targets)";
+		else if (bf.long_targets && bf.all_vs_all) why = "--long-targets does not go with --all-vs-all";
+		else if (bf.long_targets && bf.gpus > 1) why = "--long-targets runs on one GPU: it does not go with --gpus N > 1";
+		else if (bf.long_targets && (bf.scan || bf.infix || bf.keep_on)) why = "--long-targets does not go with --scan, --infix or --keep";
+		else if (bf.long_targets && bf.score_only == bf.paf) why = "--long-targets needs one of --score-only and --paf";
+		else if (bf.keep_on && bf.queries) why = "--keep does not go with --queries (it keeps pairs of --all-vs-all)";
 		else if (bf.keep_on && !bf.all_vs_all) why = "--keep goes with --all-vs-all";
 		else if (bf.keep_on && bf.gpus > 1) why = "--keep runs on one GPU: it does not go with --gpus N > 1";
 		else if (bf.keep_on && bf.min_on) why = "--keep does not go with --min-score (it is the threshold)";
@@ -1090,7 +1107,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	g_edit_infix = bf.infix;
 	if (bf.queries) {
 		k = bf.all_hits ? batch_scan_hits(opt, &bf, bf.queries, av[n - 1])
-		  : bf.scan ? batch_scan(opt, &bf, bf.queries, av[n - 1]) : batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
+		  : bf.scan || bf.long_targets ? batch_scan(opt, &bf, bf.queries, av[n - 1]) : batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
 		free(opt->sites.pos); free(opt); free(av);
 		return k;
 	}
