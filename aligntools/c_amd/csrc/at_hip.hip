@@ -7,6 +7,7 @@
 #include "at_launch.h"
 #include "at_classes.h"
 #include "at_ragplan.h"
+#include "at_queryplan.h"
 #include "at_pack.hip.h"
 #include "at_render.hip.h"
 #include "at_myers.hip.h"
@@ -25,6 +26,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
+#include <numeric>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -2139,6 +2141,25 @@ struct ReadSet {
 	int bits = 2, maxlen = 0;
 };
 
+/* hands out 256-byte-aligned typed sub-ranges of one buffer.  A function says its layout ONCE, as a function of a Carver, and carve()
+ * runs it twice: without a base, where take() only counts -- the bytes asked of grow() -- and then on the buffer */
+struct Carver {
+	char *base = nullptr;
+	size_t at = 0;
+	template <typename T> T *take(size_t n) { T *p = base ? (T *)(base + at) : nullptr; at += (n * sizeof(T) + 255) & ~(size_t)255; return p; }
+};
+
+template <typename Layout>
+static int carve(at_handle *h, void **buf, size_t *have, Layout &&layout)
+{
+	Carver count, c;
+	layout(count);
+	if (int rc = grow(h, buf, have, count.at)) return rc;
+	c.base = (char *)*buf;
+	layout(c);
+	return AT_OK;
+}
+
 /* nrev > 0: the read set also gets, as reads nreads .. nreads + nrev - 1, the reverse complements of reads 0 .. nrev - 1, made on the
  * device from their packed words (at_revcomp.hip) behind the pack kernel: no byte goes up twice */
 static int upload_reads(at_handle *h, int mode, int64_t nreads, const uint8_t *seq_blob, const int64_t *off, const int32_t *len, ReadSet *rs,
@@ -2166,17 +2187,15 @@ static int upload_reads(at_handle *h, int mode, int64_t nreads, const uint8_t *s
 	}
 	HIP_TRY(h, hipSetDevice(h->device));
 	drop_stale_error();
-	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t b_words = al((size_t)(std::max(nwords2, nwords8) + 4) * 4), b_off = al((size_t)ntot * 8), b_len = al((size_t)ntot * 4);
-	const size_t b_blob = al((size_t)blob_bytes + 32);   /* (at_pack reads whole dwords: up to 20 bytes behind the last base) */
-	int rc = grow(h, &h->d_in, &h->in_bytes, b_words + 2 * b_off + b_len + 256 + b_blob);
+	uint32_t *d_words = nullptr; int64_t *d_soff = nullptr, *d_swoff = nullptr; int32_t *d_len = nullptr; int *d_flag = nullptr; uint8_t *d_blob = nullptr;
+	int rc = carve(h, &h->d_in, &h->in_bytes, [&](Carver &c) {
+		d_words = c.take<uint32_t>((size_t)(std::max(nwords2, nwords8) + 4));
+		d_soff = c.take<int64_t>((size_t)ntot); d_swoff = c.take<int64_t>((size_t)ntot);
+		d_len = c.take<int32_t>((size_t)ntot);
+		d_flag = c.take<int>(1);
+		d_blob = c.take<uint8_t>((size_t)blob_bytes + 32);   /* (at_pack reads whole dwords: up to 20 bytes behind the last base) */
+	});
 	if (rc) return rc;
-	char *din = (char *)h->d_in;
-	uint32_t *d_words = (uint32_t *)din;
-	int64_t *d_soff = (int64_t *)(din + b_words), *d_swoff = (int64_t *)(din + b_words + b_off);
-	int32_t *d_len = (int32_t *)(din + b_words + 2 * b_off);
-	int *d_flag = (int *)(din + b_words + 2 * b_off + b_len);
-	uint8_t *d_blob = (uint8_t *)(din + b_words + 2 * b_off + b_len + 256);
 	hipStream_t s = h->stream;
 	HIP_TRY(h, hipMemcpyAsync(d_blob, seq_blob + blob_lo, (size_t)blob_bytes, hipMemcpyHostToDevice, s));
 	HIP_TRY(h, hipMemcpyAsync(d_soff, soff.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, s));
@@ -2313,61 +2332,182 @@ extern "C" int at_align_allpairs_stream(at_handle *h, int mode, int64_t nreads, 
  * per-query lists (at_search.hip).  The lists come down in one copy at the end. */
 static const char *strands_text(int strands) { return strands == AT_STRAND_REV ? ", strands=rev" : strands == AT_STRAND_BOTH ? ", strands=both" : ""; }
 
-static int search_lists(at_handle *h, int mode, int64_t nq, const int32_t *q_len, int64_t nt, const int32_t *t_len, const ReadSet &rs,
-                        int k, int use_cutoff, int32_t cutoff, int strands, int32_t *out_target, int32_t *out_score, int32_t *out_end_i,
-                        int32_t *out_end_j, int32_t *out_state, int32_t *out_strand, int32_t *out_nhits)
+/* ---- the scaffold of the query-vs-target entries (its host arithmetic: at_queryplan.h) ---- */
+struct QuerySets {
+	int64_t nq; const uint8_t *q_blob; const int64_t *q_off; const int32_t *q_len;
+	int64_t nt; const uint8_t *t_blob; const int64_t *t_off; const int32_t *t_len;
+};
+struct ListOut { int32_t *target, *score, *end_i, *end_j, *state, *strand, *nhits; };
+struct CigarOut {
+	int32_t *stats, *ncigar; int64_t *off; uint32_t *words; int64_t cap;
+	bool any() const { return stats || ncigar || off || words; }
+};
+
+/* the refusals the entries share, `who` naming the entry; each entry calls them in the order its checks always had */
+static int check_sizes(at_handle *h, const char *who, int64_t nq, int64_t nt, int64_t cigar_cap, int k = 1)
 {
-	/* strands: with a reverse strand an entry of the query order is (query << 1) | strand (at_search.hip.h); with both, a query's
-	 * two entries are adjacent, strand 0 first: same length, same block, and one run of candidates for the merge */
-	const int enc = strands != AT_STRAND_FWD, two = strands == AT_STRAND_BOTH;
-	const int64_t nv = nq << two;
-	std::vector<int> qs((size_t)nq), qperm((size_t)nv), tperm((size_t)nt);
-	for (int64_t q = 0; q < nq; ++q) qs[(size_t)q] = (int)q;
-	for (int64_t t = 0; t < nt; ++t) tperm[(size_t)t] = (int)t;
-	std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
-	std::stable_sort(tperm.begin(), tperm.end(), [&](int a, int b) { return t_len[a] < t_len[b]; });
-	for (int64_t q = 0; q < nq; ++q) {
-		const int c = qs[(size_t)q];
-		if (two) { qperm[(size_t)(2 * q)] = c << 1; qperm[(size_t)(2 * q + 1)] = (c << 1) | 1; }
-		else qperm[(size_t)q] = enc ? (c << 1) | 1 : c;
+	if (nq < 0 || nt < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "%s: negative size", who);
+	if (k < 1 || k > 64) return fail(h, AT_ERR_ARG, "%s: k = %d outside 1..64", who, k);
+	return AT_OK;
+}
+
+/* strands, tile width (0: the default, dflt_tile), flags, CIGAR outputs, read counts: no array is read */
+static int check_options(at_handle *h, const char *who, int strands, int32_t tile_cols, int dflt_tile, int flags, const CigarOut &co, int64_t nq, int64_t nt)
+{
+	if (strands < AT_STRAND_FWD || strands > AT_STRAND_BOTH) return fail(h, AT_ERR_ARG, "%s: strands = %d outside 1..3", who, strands);
+	if (tile_cols < 0 || (tile_cols & 15))
+		return fail(h, AT_ERR_ARG, "%s: tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)", who, tile_cols, dflt_tile);
+	if (flags & ~AT_CIGAR_M) return fail(h, AT_ERR_ARG, "%s: flags = %d (AT_CIGAR_M or 0)", who, flags);
+	if (co.any() && (!co.stats || !co.ncigar || !co.off || (!co.words && co.cap > 0)))
+		return fail(h, AT_ERR_ARG, "%s: the CIGAR outputs are either all NULL or all given", who);
+	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "%s: %lld queries + %lld targets: at most 2^31 - 1 reads", who, (long long)nq, (long long)nt);
+	if (strands != AT_STRAND_FWD && (nt >= (1LL << 30) || 2 * nq + nt >= (1LL << 31)))
+		return fail(h, AT_ERR_ARG, "%s: %lld queries, %lld targets: a reverse strand needs nt < 2^30 and 2 nq + nt < 2^31", who, (long long)nq, (long long)nt);
+	return AT_OK;
+}
+
+static int check_one_gpu(at_handle *h, const char *who) { return h->comm ? fail(h, AT_ERR_DOMAIN, "%s: one GPU only (this handle belongs to a multi-process job)", who) : (int)AT_OK; }
+
+static int check_list_pointers(at_handle *h, const char *who, const QuerySets &qt, const ListOut &o, bool rev)
+{
+	if (!qt.q_blob || !qt.q_off || !qt.q_len || !o.target || !o.score || !o.end_i || !o.end_j || !o.state || !o.nhits ||
+	    (rev && !o.strand) || (qt.nt > 0 && (!qt.t_blob || !qt.t_off || !qt.t_len)))
+		return fail(h, AT_ERR_ARG, "%s: NULL argument", who);
+	return AT_OK;
+}
+
+static int check_read(at_handle *h, const char *what, int64_t i, int32_t len, int64_t off, bool need_base)
+{
+	if (len < 0 || off < 0) return fail(h, AT_ERR_ARG, "%s %lld: negative length or offset", what, (long long)i);
+	if (need_base && len < 1) return fail(h, AT_ERR_DOMAIN, "%s %lld: empty", what, (long long)i);
+	return AT_OK;
+}
+
+/* "no hit" in every list entry before any work */
+static void list_out_init(const ListOut &o, int64_t nq, int k, const CigarOut &co)
+{
+	for (int64_t e = 0; e < nq * k; ++e) { o.target[e] = -1; o.score[e] = 0; o.end_i[e] = 0; o.end_j[e] = 0; o.state[e] = 0; }
+	if (o.strand) for (int64_t e = 0; e < nq * k; ++e) o.strand[e] = -1;
+	for (int64_t q = 0; q < nq; ++q) o.nhits[q] = 0;
+	if (co.any()) {
+		for (int64_t e = 0; e < nq * k; ++e) { co.ncigar[e] = 0; for (int x = 0; x < 8; ++x) co.stats[e * 8 + x] = -1; }
+		for (int64_t e = 0; e <= nq * k; ++e) co.off[e] = 0;
 	}
+}
+
+/* one read set: the queries' and the targets' bytes side by side (a copy of the input, small beside the sweep), queries first */
+static int upload_sets(at_handle *h, int mode, const QuerySets &qt, bool rev, ReadSet *rs)
+{
+	const int64_t nq = qt.nq, nr = qt.nq + qt.nt;
+	std::vector<int64_t> off((size_t)nr);
+	std::vector<int32_t> len((size_t)nr);
+	int64_t bytes = 0;
+	for (int64_t r = 0; r < nr; ++r) { off[(size_t)r] = bytes; len[(size_t)r] = r < nq ? qt.q_len[r] : qt.t_len[r - nq]; bytes += len[(size_t)r]; }
+	std::vector<uint8_t> blob((size_t)bytes + 32);
+	for (int64_t r = 0; r < nr; ++r)
+		if (len[(size_t)r]) memcpy(blob.data() + off[(size_t)r], r < nq ? qt.q_blob + qt.q_off[r] : qt.t_blob + qt.t_off[r - nq], (size_t)len[(size_t)r]);
+	return upload_reads(h, mode, nr, blob.data(), off.data(), len.data(), rs, rev ? nq : 0);
+}
+
+/* the per-query lists in h->d_str: keys, end cells and states (20 bytes per entry), behind them the merges' `bad` word.  The lists
+ * stay there behind the *_lists call: the window pass reads them */
+struct ListBufs { unsigned long long *key; int *ei, *ej, *st, *bad; size_t bkey, bl4, lbytes; };
+static int list_bufs(at_handle *h, size_t nl, bool with_bad, ListBufs *lb)
+{
+	return carve(h, &h->d_str, &h->str_bytes, [&](Carver &c) {
+		lb->key = c.take<unsigned long long>(nl); lb->bkey = c.at;
+		lb->ei = c.take<int>(nl); lb->bl4 = c.at - lb->bkey;
+		lb->ej = c.take<int>(nl); lb->st = c.take<int>(nl);
+		lb->bad = with_bad ? c.take<int>(1) : nullptr;
+		lb->lbytes = c.at;
+	});
+}
+
+/* the scores of the pairs [s0, s0 + n) of a block (entries from qa, ntb targets from ta) folded into the lists */
+static int merge_slice(at_handle *h, const at::QueryOrder &qo, const ListBufs &lb, const int *d_qperm, const int *d_tperm, int32_t *const d_res[4],
+                       int64_t s0, int64_t n, int64_t ntb, int qa, int ta, int k, int is_edit, int use_cutoff, int32_t cutoff)
+{
+	at::SearchMergeArgs ma;
+	memset(&ma, 0, sizeof ma);
+	ma.s0 = s0; ma.n = n; ma.ntb = ntb; ma.qa = qa; ma.ta = ta;
+	ma.enc = qo.enc; ma.two = qo.two; ma.qperm = d_qperm; ma.tperm = d_tperm;
+	ma.nqs = (int)((s0 + n - 1) / (ntb << qo.two) - s0 / (ntb << qo.two) + 1);
+	ma.score = d_res[0]; ma.end_i = d_res[1]; ma.end_j = d_res[2]; ma.state = d_res[3];
+	ma.k = k; ma.is_edit = is_edit; ma.use_cutoff = use_cutoff ? 1 : 0; ma.cutoff = cutoff;
+	ma.lkey = lb.key; ma.lei = lb.ei; ma.lej = lb.ej; ma.lst = lb.st; ma.bad = lb.bad;
+	HIP_TRY(h, at_search_merge_launch(&ma, h->stream));
+	return AT_OK;
+}
+
+/* the lists come down in one copy, behind the call's one wait for its sweeps, and are decoded into the caller's arrays.  negate: the
+ * ranks are negated distances; bad_who: the name under which a set `bad` word is an error, NULL: it is not looked at */
+static int lists_readback(at_handle *h, const ListBufs &lb, int64_t nq, int k, int enc, bool negate, const char *bad_who, const ListOut &o)
+{
+	std::vector<char> hl(lb.lbytes);
+	HIP_TRY(h, hipMemcpyAsync(hl.data(), lb.key, lb.lbytes, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	int bad = 0;
+	memcpy(&bad, hl.data() + lb.bkey + 3 * lb.bl4, 4);
+	if (bad && bad_who) return fail(h, AT_ERR_DOMAIN, "%s: a pair outside the domain on which the reference is defined", bad_who);
+	const unsigned long long *hk = (const unsigned long long *)hl.data();
+	const int32_t *hei = (const int32_t *)(hl.data() + lb.bkey), *hej = hei + lb.bl4 / 4, *hst = hej + lb.bl4 / 4;
+	for (int64_t q = 0; q < nq; ++q) {
+		int nh = 0;
+		for (size_t e = (size_t)q * k; nh < k && hk[e]; ++e, ++nh) {
+			const at::ListKey key = at::list_key_decode(hk[e], enc);
+			o.target[e] = key.target;
+			if (o.strand) o.strand[e] = key.strand;
+			o.score[e] = negate ? -key.rank : key.rank;
+			o.end_i[e] = hei[e]; o.end_j[e] = hej[e]; o.state[e] = hst[e];
+		}
+		o.nhits[q] = nh;
+	}
+	return AT_OK;
+}
+
+/* events on the handle's stream around a sweep phase: its device time goes into at_last_config (tools/edit_scan_rate.py and its kin) */
+struct StreamEvents {
+	hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+	~StreamEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+	int create(at_handle *h, int n) { for (int x = 0; x < n; ++x) HIP_TRY(h, hipEventCreate(&e[x])); return AT_OK; }
+};
+
+static int search_lists(at_handle *h, int mode, const QuerySets &qt, const ReadSet &rs, int k, int use_cutoff, int32_t cutoff, int strands,
+                        const ListOut &out)
+{
+	const int64_t nq = qt.nq, nt = qt.nt;
+	const int32_t *t_len = qt.t_len;
+	const at::QueryOrder qo = at::query_order(nq, qt.q_len, strands);
+	std::vector<int> tperm((size_t)nt);
+	std::iota(tperm.begin(), tperm.end(), 0);
+	std::stable_sort(tperm.begin(), tperm.end(), [&](int a, int b) { return t_len[a] < t_len[b]; });
 	std::vector<int32_t> tls((size_t)nt);
 	for (int64_t t = 0; t < nt; ++t) tls[(size_t)t] = t_len[tperm[(size_t)t]];
 	struct Block { int qa, nqb, ta; int64_t ntb; int32_t l1, l2; bool uniform; };
 	std::vector<Block> blocks;
 	int64_t most = 0;
-	for (int64_t a = 0, b; a < nq; a = b) {
-		const int32_t L = q_len[qs[(size_t)a]];
-		for (b = a; b < nq && q_len[qs[(size_t)b]] == L; ++b) {}
-		const int64_t ta = mode == AT_MODE_FIT ? std::lower_bound(tls.begin(), tls.end(), L) - tls.begin() : 0;
+	for (const at::QueryBlock &Q : qo.blocks) {
+		const int64_t ta = mode == AT_MODE_FIT ? std::lower_bound(tls.begin(), tls.end(), Q.l1) - tls.begin() : 0;
 		if (ta == nt) continue;                                   /* fit: every target is shorter than these queries */
-		blocks.push_back({(int)(a << two), (int)((b - a) << two), (int)ta, nt - ta, L, tls.back(), tls[(size_t)ta] == tls.back()});
-		most = std::max<int64_t>(most, ((b - a) << two) * (nt - ta));
+		blocks.push_back({Q.qa, Q.nqb, (int)ta, nt - ta, Q.l1, tls.back(), tls[(size_t)ta] == tls.back()});
+		most = std::max<int64_t>(most, (int64_t)Q.nqb * (nt - ta));
 	}
-	int64_t chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
-	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(std::max<int64_t>(most, 1), 1LL << 28)));
-	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	/* descriptors (24 bytes per pair of a slice) and both permutations; results (16 bytes per pair); the lists (20 bytes per entry) + flag */
-	const size_t b8 = al((size_t)chunk * 8), b4 = al((size_t)chunk * 4), bq = al((size_t)nv * 4), bt = al((size_t)nt * 4);
-	const size_t nl = (size_t)nq * (size_t)k, bkey = al(nl * 8), bl4 = al(nl * 4);
-	int rc = grow(h, &h->d_desc, &h->desc_bytes, 2 * b8 + 2 * b4 + bq + bt);
+	const int64_t chunk = at::slice_clamp(env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault), most);
+	/* descriptors (24 bytes per pair of a slice) and both permutations; results (16 bytes per pair); the lists + flag */
+	int64_t *d_woff1 = nullptr, *d_woff2 = nullptr; int32_t *d_len1 = nullptr, *d_len2 = nullptr, *d_r[4]; int *d_qperm = nullptr, *d_tperm = nullptr;
+	ListBufs lb;
+	int rc = carve(h, &h->d_desc, &h->desc_bytes, [&](Carver &c) {
+		d_woff1 = c.take<int64_t>((size_t)chunk); d_woff2 = c.take<int64_t>((size_t)chunk);
+		d_len1 = c.take<int32_t>((size_t)chunk); d_len2 = c.take<int32_t>((size_t)chunk);
+		d_qperm = c.take<int>((size_t)qo.nv); d_tperm = c.take<int>((size_t)nt);
+	});
+	if (!rc) rc = carve(h, &h->d_out, &h->out_bytes, [&](Carver &c) { for (int32_t *&x : d_r) x = c.take<int32_t>((size_t)chunk); });
+	if (!rc) rc = list_bufs(h, (size_t)nq * (size_t)k, true, &lb);
 	if (rc) return rc;
-	rc = grow(h, &h->d_out, &h->out_bytes, 4 * b4);
-	if (rc) return rc;
-	const size_t lbytes = bkey + 3 * bl4 + 256;
-	rc = grow(h, &h->d_str, &h->str_bytes, lbytes);
-	if (rc) return rc;
-	char *dd = (char *)h->d_desc, *dr = (char *)h->d_out, *dl = (char *)h->d_str;
-	int64_t *d_woff1 = (int64_t *)dd, *d_woff2 = (int64_t *)(dd + b8);
-	int32_t *d_len1 = (int32_t *)(dd + 2 * b8), *d_len2 = (int32_t *)(dd + 2 * b8 + b4);
-	int *d_qperm = (int *)(dd + 2 * b8 + 2 * b4), *d_tperm = (int *)(dd + 2 * b8 + 2 * b4 + bq);
-	int32_t *d_sc = (int32_t *)dr, *d_ei = (int32_t *)(dr + b4), *d_ej = (int32_t *)(dr + 2 * b4), *d_st = (int32_t *)(dr + 3 * b4);
-	unsigned long long *d_key = (unsigned long long *)dl;
-	int *d_lei = (int *)(dl + bkey), *d_lej = (int *)(dl + bkey + bl4), *d_lst = (int *)(dl + bkey + 2 * bl4), *d_bad = (int *)(dl + bkey + 3 * bl4);
 	hipStream_t s = h->stream;
-	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nv * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_qperm, qo.qperm.data(), (size_t)qo.nv * 4, hipMemcpyHostToDevice, s));
 	HIP_TRY(h, hipMemcpyAsync(d_tperm, tperm.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemsetAsync(dl, 0, lbytes, s));
+	HIP_TRY(h, hipMemsetAsync(lb.key, 0, lb.lbytes, s));
 	std::string cfg0;
 	int64_t nslices = 0;
 	for (const Block &B : blocks) {
@@ -2376,50 +2516,21 @@ static int search_lists(at_handle *h, int mode, int64_t nq, const int32_t *q_len
 			const int64_t n = std::min(chunk, bp - s0);
 			at::SearchDescArgs da;
 			memset(&da, 0, sizeof da);
-			da.s0 = s0; da.n = n; da.ntb = B.ntb; da.qa = B.qa; da.ta = B.ta; da.nq = (int)nq; da.enc = enc; da.nrev0 = (int)(nq + nt);
+			da.s0 = s0; da.n = n; da.ntb = B.ntb; da.qa = B.qa; da.ta = B.ta; da.nq = (int)nq; da.enc = qo.enc; da.nrev0 = (int)(nq + nt);
 			da.qperm = d_qperm; da.tperm = d_tperm; da.swoff = (const long long *)rs.d_swoff; da.slen = rs.d_len;
 			da.woff1 = (long long *)d_woff1; da.woff2 = (long long *)d_woff2; da.len1 = d_len1; da.len2 = d_len2;
 			HIP_TRY(h, at_search_desc_launch(&da, h->ncu, s));
 			rc = align_device(h, mode, n, rs.d_words, rs.bits, d_woff1, d_len1, d_woff2, d_len2, B.l1, B.l2, B.uniform ? 1 : 0, 0,
-			                  d_sc, d_ei, d_ej, d_st, nullptr, nullptr, nullptr, s, 0, 0);
+			                  d_r[0], d_r[1], d_r[2], d_r[3], nullptr, nullptr, nullptr, s, 0, 0);
 			if (rc) { (void)hipStreamSynchronize(s); return rc; }
 			if (nslices == 0) cfg0 = h->cfg;
-			at::SearchMergeArgs ma;
-			memset(&ma, 0, sizeof ma);
-			ma.s0 = s0; ma.n = n; ma.ntb = B.ntb; ma.qa = B.qa; ma.ta = B.ta;
-			ma.enc = enc; ma.two = two;
-			ma.nqs = (int)((s0 + n - 1) / (B.ntb << two) - s0 / (B.ntb << two) + 1);
-			ma.qperm = d_qperm; ma.tperm = d_tperm;
-			ma.score = d_sc; ma.end_i = d_ei; ma.end_j = d_ej; ma.state = d_st;
-			ma.k = k; ma.is_edit = mode == AT_MODE_EDIT; ma.use_cutoff = use_cutoff ? 1 : 0; ma.cutoff = cutoff;
-			ma.lkey = d_key; ma.lei = d_lei; ma.lej = d_lej; ma.lst = d_lst; ma.bad = d_bad;
-			HIP_TRY(h, at_search_merge_launch(&ma, s));
+			rc = merge_slice(h, qo, lb, d_qperm, d_tperm, d_r, s0, n, B.ntb, B.qa, B.ta, k, mode == AT_MODE_EDIT, use_cutoff, cutoff);
+			if (rc) return rc;
 			++nslices;
 		}
 	}
-	std::vector<char> hl(lbytes);
-	HIP_TRY(h, hipMemcpyAsync(hl.data(), dl, lbytes, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipStreamSynchronize(s));
-	int bad = 0;
-	memcpy(&bad, hl.data() + bkey + 3 * bl4, 4);
-	if (bad) return fail(h, AT_ERR_DOMAIN, "search: a pair outside the domain on which the reference is defined");
-	const unsigned long long *hk = (const unsigned long long *)hl.data();
-	const int32_t *hei = (const int32_t *)(hl.data() + bkey), *hej = (const int32_t *)(hl.data() + bkey + bl4), *hst = (const int32_t *)(hl.data() + bkey + 2 * bl4);
-	for (int64_t q = 0; q < nq; ++q) {
-		int nh = 0;
-		for (int j = 0; j < k; ++j) {
-			const size_t e = (size_t)q * k + j;
-			if (!hk[e]) break;
-			const int32_t r = (int32_t)((uint32_t)(hk[e] >> 32) ^ 0x80000000u);
-			const uint32_t low = ~(uint32_t)hk[e];
-			out_target[e] = (int32_t)(low >> enc);
-			if (out_strand) out_strand[e] = enc ? (int32_t)(low & 1u) : 0;
-			out_score[e] = mode == AT_MODE_EDIT ? -r : r;
-			out_end_i[e] = hei[e]; out_end_j[e] = hej[e]; out_state[e] = hst[e];
-			++nh;
-		}
-		out_nhits[q] = nh;
-	}
+	rc = lists_readback(h, lb, nq, k, qo.enc, mode == AT_MODE_EDIT, "search", out);
+	if (rc) return rc;
 	snprintf(h->cfg, sizeof h->cfg, "search: %lld blocks, %lld slices, k=%d%s; %.560s", (long long)blocks.size(), (long long)nslices, k,
 	         strands_text(strands), cfg0.c_str());
 	return AT_OK;
@@ -2432,52 +2543,25 @@ extern "C" int at_search_strands(at_handle *h, int mode,
                                  int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
                                  int32_t *out_state, int32_t *out_strand, int32_t *out_nhits)
 {
+	const char *who = "at_search";
 	if (!h) return fail(nullptr, AT_ERR_ARG, "at_search: NULL handle");
 	if (mode < AT_MODE_GLOBAL || mode > AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "unknown mode %d", mode);
-	if (nq < 0 || nt < 0) return fail(h, AT_ERR_ARG, "at_search: negative size");
-	if (k < 1 || k > 64) return fail(h, AT_ERR_ARG, "at_search: k = %d outside 1..64", k);
-	if (strands < AT_STRAND_FWD || strands > AT_STRAND_BOTH) return fail(h, AT_ERR_ARG, "at_search: strands = %d outside 1..3", strands);
+	const QuerySets qt = {nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len};
+	const ListOut out = {out_target, out_score, out_end_i, out_end_j, out_state, out_strand, out_nhits};
+	int rc = check_sizes(h, who, nq, nt, 0, k);
+	if (rc || (rc = check_options(h, who, strands, 0, 0, 0, CigarOut{}, nq, nt))) return rc;
 	const bool rev = strands != AT_STRAND_FWD;
-	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "at_search: %lld queries + %lld targets: at most 2^31 - 1 reads", (long long)nq, (long long)nt);
-	if (rev && (nt >= (1LL << 30) || 2 * nq + nt >= (1LL << 31)))
-		return fail(h, AT_ERR_ARG, "at_search: %lld queries, %lld targets: a reverse strand needs nt < 2^30 and 2 nq + nt < 2^31", (long long)nq, (long long)nt);
 	if (nq == 0) return AT_OK;
-	if (!q_blob || !q_off || !q_len || !out_target || !out_score || !out_end_i || !out_end_j || !out_state || !out_nhits ||
-	    (rev && !out_strand) || (nt > 0 && (!t_blob || !t_off || !t_len)))
-		return fail(h, AT_ERR_ARG, "at_search: NULL argument");
+	if ((rc = check_list_pointers(h, who, qt, out, rev))) return rc;
 	const bool need_base = mode == AT_MODE_LOCAL || mode == AT_MODE_OVERLAP;   /* (as upload_reads) */
-	for (int64_t q = 0; q < nq; ++q) {
-		if (q_len[q] < 0 || q_off[q] < 0) return fail(h, AT_ERR_ARG, "query %lld: negative length or offset", (long long)q);
-		if (need_base && q_len[q] < 1) return fail(h, AT_ERR_DOMAIN, "query %lld: empty", (long long)q);
-	}
-	for (int64_t t = 0; t < nt; ++t) {
-		if (t_len[t] < 0 || t_off[t] < 0) return fail(h, AT_ERR_ARG, "target %lld: negative length or offset", (long long)t);
-		if (need_base && t_len[t] < 1) return fail(h, AT_ERR_DOMAIN, "target %lld: empty", (long long)t);
-	}
-	return guarded(h, "at_search", [&]() -> int {
-		for (int64_t e = 0; e < nq * k; ++e) { out_target[e] = -1; out_score[e] = 0; out_end_i[e] = 0; out_end_j[e] = 0; out_state[e] = 0; }
-		if (out_strand) for (int64_t e = 0; e < nq * k; ++e) out_strand[e] = -1;
-		for (int64_t q = 0; q < nq; ++q) out_nhits[q] = 0;
+	for (int64_t q = 0; q < nq; ++q) if ((rc = check_read(h, "query", q, q_len[q], q_off[q], need_base))) return rc;
+	for (int64_t t = 0; t < nt; ++t) if ((rc = check_read(h, "target", t, t_len[t], t_off[t], need_base))) return rc;
+	return guarded(h, who, [&]() -> int {
+		list_out_init(out, nq, k, CigarOut{});
 		if (nt == 0) { snprintf(h->cfg, sizeof h->cfg, "search: 0 blocks, 0 slices, k=%d%s; ", k, strands_text(strands)); return (int)AT_OK; }
-		/* one read set: the queries' and the targets' bytes side by side (a copy of the input, small beside the sweep) */
-		int64_t bytes = 0;
-		for (int64_t q = 0; q < nq; ++q) bytes += q_len[q];
-		for (int64_t t = 0; t < nt; ++t) bytes += t_len[t];
-		std::vector<uint8_t> blob((size_t)bytes + 32);
-		std::vector<int64_t> off((size_t)(nq + nt));
-		std::vector<int32_t> len((size_t)(nq + nt));
-		int64_t at = 0;
-		for (int64_t r = 0; r < nq + nt; ++r) {
-			const bool isq = r < nq;
-			const int32_t l = isq ? q_len[r] : t_len[r - nq];
-			if (l) memcpy(blob.data() + at, isq ? q_blob + q_off[r] : t_blob + t_off[r - nq], (size_t)l);
-			off[(size_t)r] = at; len[(size_t)r] = l; at += l;
-		}
 		ReadSet rs;
-		int rc = upload_reads(h, mode, nq + nt, blob.data(), off.data(), len.data(), &rs, rev ? nq : 0);
-		if (rc) return rc;
-		return search_lists(h, mode, nq, q_len, nt, t_len, rs, k, use_cutoff, cutoff, strands, out_target, out_score, out_end_i, out_end_j,
-		                    out_state, out_strand, out_nhits);
+		if (int rc2 = upload_sets(h, mode, qt, rev, &rs)) return rc2;
+		return search_lists(h, mode, qt, rs, k, use_cutoff, cutoff, strands, out);
 	});
 }
 
@@ -2509,150 +2593,165 @@ extern "C" int at_scan_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t 
 
 static const char *scan_strands_text(int strands) { return strands == AT_STRAND_REV ? "rev" : strands == AT_STRAND_BOTH ? "both" : "fwd"; }
 
-/* the lists of at_scan: the blocks and slices of search_lists with the targets in caller order; per slice the key slots are set,
- * the groups of its pairs swept, the keys unpacked and merged (at_scan.hip.h).  The lists stay in h->d_str behind the call. */
-static int scan_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64_t nt, const int32_t *t_len, const ReadSet &rs,
-                      int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile, int32_t *out_target, int32_t *out_score,
-                      int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state, int32_t *out_strand, int32_t *out_nhits,
-                      size_t *list_bkey, size_t *list_b4)
-{
-	const int enc = strands != AT_STRAND_FWD, two = strands == AT_STRAND_BOTH;
-	const int64_t nv = nq << two;
-	std::vector<int> qs((size_t)nq), qperm((size_t)nv), tperm((size_t)nt);
-	for (int64_t q = 0; q < nq; ++q) qs[(size_t)q] = (int)q;
-	for (int64_t t = 0; t < nt; ++t) tperm[(size_t)t] = (int)t;
-	std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
-	for (int64_t q = 0; q < nq; ++q) {
-		const int c = qs[(size_t)q];
-		if (two) { qperm[(size_t)(2 * q)] = c << 1; qperm[(size_t)(2 * q + 1)] = (c << 1) | 1; }
-		else qperm[(size_t)q] = enc ? (c << 1) | 1 : c;
+/* what the sweeps of at_scan and at_scan_hits share: the targets' group prefix (gpre[t]: groups in front of target t, gall: of all), the
+ * items in front of a pair, a block's kernel class and occupancy, a slice's arguments and grid, the first slice's words */
+struct ScanSweep {
+	int64_t nq, nt;
+	int enc, tile, w, occ;   /* w, occ: of the block at hand */
+	const ReadSet &rs;
+	std::vector<long long> gpre;
+	long long gall;
+	ScanSweep(const QuerySets &qt, int enc_, int32_t tile_, const ReadSet &rs_) : nq(qt.nq), nt(qt.nt), enc(enc_), tile(tile_), w(0), occ(0), rs(rs_), gpre((size_t)qt.nt + 1, 0)
+	{
+		for (int64_t t = 0; t < nt; ++t) gpre[(size_t)t + 1] = gpre[(size_t)t] + at::scan_groups(qt.t_len[t], tile);
+		gall = gpre[(size_t)nt];
 	}
-	std::vector<long long> gpre((size_t)nt + 1);
-	gpre[0] = 0;
-	for (int64_t t = 0; t < nt; ++t) gpre[(size_t)t + 1] = gpre[(size_t)t] + at::scan_groups(t_len[t], tile);
-	const long long gall = gpre[(size_t)nt];
-	struct Block { int qa, nqb; int32_t l1; };
-	std::vector<Block> blocks;
-	int64_t most = 0;
-	for (int64_t a = 0, b; a < nq; a = b) {
-		const int32_t L = q_len[qs[(size_t)a]];
-		for (b = a; b < nq && q_len[qs[(size_t)b]] == L; ++b) {}
-		blocks.push_back({(int)(a << two), (int)((b - a) << two), L});
-		most = std::max<int64_t>(most, ((b - a) << two) * nt);
-	}
-	int64_t chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
-	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(std::max<int64_t>(most, 1), 1LL << 28)));
-	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t b8 = al((size_t)chunk * 8), b4 = al((size_t)chunk * 4), bq = al((size_t)nv * 4), bt = al((size_t)nt * 4), bg = al(((size_t)nt + 1) * 8);
-	const size_t nl = (size_t)nq * (size_t)k, bkey = al(nl * 8), bl4 = al(nl * 4);
-	int rc = grow(h, &h->d_desc, &h->desc_bytes, b8 + bg + bq + bt);
-	if (rc) return rc;
-	rc = grow(h, &h->d_out, &h->out_bytes, 4 * b4);
-	if (rc) return rc;
-	const size_t lbytes = bkey + 3 * bl4 + 256;
-	rc = grow(h, &h->d_str, &h->str_bytes, lbytes);
-	if (rc) return rc;
-	char *dd = (char *)h->d_desc, *dr = (char *)h->d_out, *dl = (char *)h->d_str;
-	unsigned long long *d_pkey = (unsigned long long *)dd;
-	long long *d_gpre = (long long *)(dd + b8);
-	int *d_qperm = (int *)(dd + b8 + bg), *d_tperm = (int *)(dd + b8 + bg + bq);
-	int32_t *d_sc = (int32_t *)dr, *d_ei = (int32_t *)(dr + b4), *d_ej = (int32_t *)(dr + 2 * b4), *d_st = (int32_t *)(dr + 3 * b4);
-	unsigned long long *d_key = (unsigned long long *)dl;
-	int *d_lei = (int *)(dl + bkey), *d_lej = (int *)(dl + bkey + bl4), *d_lst = (int *)(dl + bkey + 2 * bl4), *d_bad = (int *)(dl + bkey + 3 * bl4);
-	hipStream_t s = h->stream;
-	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nv * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemcpyAsync(d_tperm, tperm.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemcpyAsync(d_gpre, gpre.data(), ((size_t)nt + 1) * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemsetAsync(dl, 0, lbytes, s));
-	std::string cfg0;
-	int64_t nslices = 0;
-	int ov_most = 0;
-	/* the device time of the sweep phase (key slots, groups, unpack, merge of every slice) goes into at_last_config: tools/edit_scan_rate.py */
-	struct Ev { hipEvent_t e[2] = {nullptr, nullptr}; ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
-	for (hipEvent_t &x : ev.e) HIP_TRY(h, hipEventCreate(&x));
-	HIP_TRY(h, hipEventRecord(ev.e[0], s));
-	auto items_before = [&](int64_t x) { return (long long)(x / nt) * gall + gpre[(size_t)(x % nt)]; };   /* items of the block's pairs [0, x) */
-	for (const Block &B : blocks) {
-		const int64_t bp = (int64_t)B.nqb * nt;
-		const int w = at::class_rows(at::kMyersLaneWords, B.l1);
-		const void *fn = at_scan_kernel(w);
+	long long items_before(int64_t x) const { return (long long)(x / nt) * gall + gpre[(size_t)(x % nt)]; }   /* items of the block's pairs [0, x) */
+	int block(at_handle *h, int32_t l1, const void *(*kernel)(int))
+	{
+		w = at::class_rows(at::kMyersLaneWords, l1);
+		const void *fn = kernel(w);
 		if (!fn) return fail(h, AT_ERR_ARG, "no scan kernel for %d words per lane", w);
-		int occ = 0;
+		occ = 0;
 		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64, 0) != hipSuccess || occ <= 0) occ = 8;
-		ov_most = std::max(ov_most, (int)at::scan_overlap(B.l1, use_cutoff, cutoff));
+		return AT_OK;
+	}
+	at::ScanArgs slice(int qa, int64_t s0, int64_t n, const long long *d_gpre, const int *d_qperm, int use_cutoff, int32_t cutoff) const
+	{
+		at::ScanArgs sa;
+		memset(&sa, 0, sizeof sa);
+		sa.y0 = items_before(s0); sa.nitems = items_before(s0 + n) - sa.y0;
+		sa.s0 = s0; sa.npairs = n; sa.ntb = nt; sa.gall = gall; sa.gpre = d_gpre;
+		sa.qa = qa; sa.nq = (int)nq; sa.enc = enc; sa.nrev0 = (int)(nq + nt); sa.qperm = d_qperm;
+		sa.seq = rs.d_words; sa.swoff = (const long long *)rs.d_swoff; sa.slen = rs.d_len;
+		sa.tile = tile; sa.use_cutoff = use_cutoff ? 1 : 0; sa.cutoff = cutoff;
+		return sa;
+	}
+	long long grid(const at_handle *h, const at::ScanArgs &sa) const { return std::max(1LL, std::min<long long>(sa.nitems, (long long)occ * h->ncu)); }
+	std::string text(const char *kernel, long long grid) const
+	{
+		return std::string(kernel) + " bits=2 words/lane=" + std::to_string(w) + " (1 read/wave, 64 tiles) lds=0B waves/cu<=" + std::to_string(occ) + " grid=" + std::to_string(grid);
+	}
+};
+
+/* the lists of at_scan: the blocks and slices of search_lists with the targets in caller order; per slice the key slots are set,
+ * the groups of its pairs swept, the keys unpacked and merged (at_scan.hip.h).  (The merges' `bad` word is not looked at.) */
+static int scan_lists(at_handle *h, const QuerySets &qt, const ReadSet &rs, int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile,
+                      const ListOut &out, ListBufs &lb)
+{
+	const int64_t nq = qt.nq, nt = qt.nt;
+	const at::QueryOrder qo = at::query_order(nq, qt.q_len, strands);
+	std::vector<int> tperm((size_t)nt);   /* (the targets stay in caller order) */
+	std::iota(tperm.begin(), tperm.end(), 0);
+	ScanSweep sw(qt, qo.enc, tile, rs);
+	int64_t most = 0;
+	for (const at::QueryBlock &B : qo.blocks) most = std::max<int64_t>(most, (int64_t)B.nqb * nt);
+	const int64_t chunk = at::slice_clamp(env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault), most);
+	unsigned long long *d_pkey = nullptr; long long *d_gpre = nullptr; int *d_qperm = nullptr, *d_tperm = nullptr; int32_t *d_r[4];
+	int rc = carve(h, &h->d_desc, &h->desc_bytes, [&](Carver &c) {
+		d_pkey = c.take<unsigned long long>((size_t)chunk); d_gpre = c.take<long long>((size_t)nt + 1);
+		d_qperm = c.take<int>((size_t)qo.nv); d_tperm = c.take<int>((size_t)nt);
+	});
+	if (!rc) rc = carve(h, &h->d_out, &h->out_bytes, [&](Carver &c) { for (int32_t *&x : d_r) x = c.take<int32_t>((size_t)chunk); });
+	if (!rc) rc = list_bufs(h, (size_t)nq * (size_t)k, true, &lb);
+	if (rc) return rc;
+	hipStream_t s = h->stream;
+	HIP_TRY(h, hipMemcpyAsync(d_qperm, qo.qperm.data(), (size_t)qo.nv * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_tperm, tperm.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_gpre, sw.gpre.data(), ((size_t)nt + 1) * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemsetAsync(lb.key, 0, lb.lbytes, s));
+	std::string cfg0;
+	int64_t nslices = 0, ov_most = 0;
+	StreamEvents ev;   /* (around key slots, groups, unpack and merge of every slice) */
+	if ((rc = ev.create(h, 2))) return rc;
+	HIP_TRY(h, hipEventRecord(ev.e[0], s));
+	for (const at::QueryBlock &B : qo.blocks) {
+		const int64_t bp = (int64_t)B.nqb * nt;
+		if ((rc = sw.block(h, B.l1, at_scan_kernel))) return rc;
+		ov_most = std::max<int64_t>(ov_most, at::scan_overlap(B.l1, use_cutoff, cutoff));
 		for (int64_t s0 = 0; s0 < bp; s0 += chunk) {
 			const int64_t n = std::min(chunk, bp - s0);
-			at::ScanArgs sa;
-			memset(&sa, 0, sizeof sa);
-			sa.y0 = items_before(s0); sa.nitems = items_before(s0 + n) - sa.y0;
-			sa.s0 = s0; sa.npairs = n; sa.ntb = nt; sa.gall = gall; sa.gpre = d_gpre;
-			sa.qa = B.qa; sa.nq = (int)nq; sa.enc = enc; sa.nrev0 = (int)(nq + nt); sa.qperm = d_qperm;
-			sa.seq = rs.d_words; sa.swoff = (const long long *)rs.d_swoff; sa.slen = rs.d_len;
-			sa.tile = tile; sa.use_cutoff = use_cutoff ? 1 : 0; sa.cutoff = cutoff;
-			sa.key = d_pkey; sa.score = d_sc; sa.end_i = d_ei; sa.end_j = d_ej; sa.state = d_st;
+			at::ScanArgs sa = sw.slice(B.qa, s0, n, d_gpre, d_qperm, use_cutoff, cutoff);
+			sa.key = d_pkey; sa.score = d_r[0]; sa.end_i = d_r[1]; sa.end_j = d_r[2]; sa.state = d_r[3];
 			HIP_TRY(h, at_scan_init_launch(&sa, h->ncu, s));
 			if (int rcq = ensure_queue(h, s)) return rcq;
 			sa.queue = h->d_queue;
-			const long long grid = std::max(1LL, std::min<long long>(sa.nitems, (long long)occ * h->ncu));
-			HIP_TRY(h, at_scan_launch(&sa, w, (unsigned)grid, s));
+			const long long grid = sw.grid(h, sa);
+			HIP_TRY(h, at_scan_launch(&sa, sw.w, (unsigned)grid, s));
 			HIP_TRY(h, at_scan_unpack_launch(&sa, h->ncu, s));
-			if (nslices == 0) {
-				char buf[200];
-				snprintf(buf, sizeof buf, "myers-scan bits=2 words/lane=%d (1 read/wave, 64 tiles) lds=0B waves/cu<=%d grid=%lld", w, occ, grid);
-				cfg0 = buf;
-			}
-			at::SearchMergeArgs ma;
-			memset(&ma, 0, sizeof ma);
-			ma.s0 = s0; ma.n = n; ma.ntb = nt; ma.qa = B.qa; ma.ta = 0;
-			ma.enc = enc; ma.two = two;
-			ma.nqs = (int)((s0 + n - 1) / (nt << two) - s0 / (nt << two) + 1);
-			ma.qperm = d_qperm; ma.tperm = d_tperm;
-			ma.score = d_sc; ma.end_i = d_ei; ma.end_j = d_ej; ma.state = d_st;
-			ma.k = k; ma.is_edit = 1; ma.use_cutoff = use_cutoff ? 1 : 0; ma.cutoff = cutoff;
-			ma.lkey = d_key; ma.lei = d_lei; ma.lej = d_lej; ma.lst = d_lst; ma.bad = d_bad;
-			HIP_TRY(h, at_search_merge_launch(&ma, s));
+			if (nslices == 0) cfg0 = sw.text("myers-scan", grid);
+			if ((rc = merge_slice(h, qo, lb, d_qperm, d_tperm, d_r, s0, n, nt, B.qa, 0, k, 1, use_cutoff, cutoff))) return rc;
 			++nslices;
 		}
 	}
 	HIP_TRY(h, hipEventRecord(ev.e[1], s));
-	std::vector<char> hl(lbytes);
-	HIP_TRY(h, hipMemcpyAsync(hl.data(), dl, lbytes, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipStreamSynchronize(s));
+	if ((rc = lists_readback(h, lb, nq, k, qo.enc, true, nullptr, out))) return rc;
 	float sweep_ms = 0.f;
 	HIP_TRY(h, hipEventElapsedTime(&sweep_ms, ev.e[0], ev.e[1]));
-	const unsigned long long *hk = (const unsigned long long *)hl.data();
-	const int32_t *hei = (const int32_t *)(hl.data() + bkey), *hej = (const int32_t *)(hl.data() + bkey + bl4), *hst = (const int32_t *)(hl.data() + bkey + 2 * bl4);
-	for (int64_t q = 0; q < nq; ++q) {
-		int nh = 0;
-		for (int j = 0; j < k; ++j) {
-			const size_t e = (size_t)q * k + j;
-			if (!hk[e]) break;
-			const int32_t r = (int32_t)((uint32_t)(hk[e] >> 32) ^ 0x80000000u);
-			const uint32_t low = ~(uint32_t)hk[e];
-			out_target[e] = (int32_t)(low >> enc);
-			if (out_strand) out_strand[e] = enc ? (int32_t)(low & 1u) : 0;
-			out_score[e] = -r;
-			out_end_i[e] = hei[e]; out_end_j[e] = hej[e]; out_state[e] = hst[e];
-			++nh;
-		}
-		out_nhits[q] = nh;
+	snprintf(h->cfg, sizeof h->cfg, "scan: tile=%d overlap<=%d groups=%lld k=%d strands=%s, %lld blocks, %lld slices; %s sweep=%.3fms", tile, (int)ov_most, sw.gall, k,
+	         scan_strands_text(strands), (long long)qo.blocks.size(), (long long)nslices, cfg0.c_str(), (double)sweep_ms);
+	return AT_OK;
+}
+
+/* what the window passes (the alignments of hits) share.  window_carve: the device arrays, in h->d_out [front bytes |] three 64-bit arrays
+ * [| the hits' list entries] | eight 32-bit arrays, in h->d_cg the run counts [| a second set] | statistics | word offsets | the words for
+ * dcap | `bad`, and the op slots in a buffer the family names.  window_fetch: counts, statistics and offsets into the caller's arrays
+ * behind the pass's one wait; a set `bad` word is bad_text.  window_words: the words that end within the caller's room */
+struct WindowBufs {
+	void *front; int64_t *woff1, *woff2, *ops_off, *coff; long long *eidx; uint32_t *cigar; int *bad; uint8_t *ops;
+	int32_t *len1, *len2, *aux, *sc, *ei, *ej, *st, *nops, *ncigar, *ncout, *stats;   /* aux: the windows' starts, or the pairs' slot sizes */
+};
+
+static int window_carve(at_handle *h, int64_t n, int64_t dcap, size_t front_bytes, bool eidx, bool ncout, void **ops_buf, size_t *ops_have, size_t ops_need,
+                        WindowBufs &w)
+{
+	int rc = carve(h, &h->d_out, &h->out_bytes, [&](Carver &c) {
+		w.front = c.take<char>(front_bytes);
+		w.woff1 = c.take<int64_t>((size_t)n + 1); w.woff2 = c.take<int64_t>((size_t)n + 1); w.ops_off = c.take<int64_t>((size_t)n + 1);
+		w.eidx = eidx ? c.take<long long>((size_t)n + 1) : nullptr;
+		for (int32_t **x : {&w.len1, &w.len2, &w.aux, &w.sc, &w.ei, &w.ej, &w.st, &w.nops}) *x = c.take<int32_t>((size_t)n);
+	});
+	if (!rc) rc = grow(h, ops_buf, ops_have, ops_need);
+	if (!rc) rc = carve(h, &h->d_cg, &h->cg_bytes, [&](Carver &c) {
+		w.ncigar = c.take<int32_t>((size_t)n);
+		w.ncout = ncout ? c.take<int32_t>((size_t)n) : w.ncigar;
+		w.stats = c.take<int32_t>((size_t)n * 8); w.coff = c.take<int64_t>((size_t)n + 1);
+		w.cigar = c.take<uint32_t>((size_t)dcap); w.bad = c.take<int>(1);
+	});
+	w.ops = (uint8_t *)*ops_buf;
+	return rc;
+}
+
+static int window_fetch(at_handle *h, const WindowBufs &w, int64_t n, const char *bad_text, int32_t *out_ncigar, int32_t *out_stats, int64_t *out_off)
+{
+	int bad = 0;
+	hipStream_t s = h->stream;
+	HIP_TRY(h, hipMemcpyAsync(&bad, w.bad, 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipMemcpyAsync(out_ncigar, w.ncout, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipMemcpyAsync(out_stats, w.stats, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipMemcpyAsync(out_off, w.coff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(h, hipStreamSynchronize(s));
+	return bad ? fail(h, AT_ERR_RANGE, "%s", bad_text) : (int)AT_OK;
+}
+
+static int window_words(at_handle *h, const WindowBufs &w, const int64_t *off, int64_t n, int64_t room, uint32_t *out_cigar)
+{
+	const int64_t fit = at::prefix_fit(off, n, room);
+	if (fit > 0) {
+		HIP_TRY(h, hipMemcpyAsync(out_cigar, w.cigar, (size_t)fit * 4, hipMemcpyDeviceToHost, h->stream));
+		HIP_TRY(h, hipStreamSynchronize(h->stream));
 	}
-	snprintf(h->cfg, sizeof h->cfg, "scan: tile=%d overlap<=%d groups=%lld k=%d strands=%s, %lld blocks, %lld slices; %s sweep=%.3fms", tile, ov_most, gall, k,
-	         scan_strands_text(strands), (long long)blocks.size(), (long long)nslices, cfg0.c_str(), (double)sweep_ms);
-	*list_bkey = bkey; *list_b4 = bl4;
 	return AT_OK;
 }
 
 /* the alignments of the hits: every list entry as a window pair through at_infix<W, true> and the CIGAR kernels (at_scan.hip.h) */
 /* at_scan: the n = nq * k list entries, entry e of query e / k, windows that end in their arg-min.  at_scan_hits (who names the caller
- * in an error text): n hits with their queries in d_eq and END-ANCHORED windows -- a hit that is not the best of its triple is not the
+ * in an error text): n hits with their queries in lb.ei and END-ANCHORED windows -- a hit that is not the best of its triple is not the
  * arg-min of its window */
-static int scan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadSet &rs, int64_t nt, int32_t maxq, size_t bkey, size_t bl4,
+static int scan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadSet &rs, int64_t nt, int32_t maxq, const ListBufs &lb,
                        const int32_t *out_target, const int32_t *out_score, const int32_t *out_end_i, const int32_t *out_end_j, int flags,
-                       int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap,
-                       int64_t nhits = -1, const int *d_eq = nullptr, const char *who = "at_scan")
+                       const CigarOut &co, int64_t nhits = -1, const char *who = "at_scan")
 {
-	const int enc = strands != AT_STRAND_FWD;
 	const int64_t n = nhits >= 0 ? nhits : nq * k;
 	const int anchor = nhits >= 0 ? 1 : 0;
 	/* ops slots: l1 + window columns per hit, back to back */
@@ -2666,65 +2765,38 @@ static int scan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadS
 		ops_bytes += (int64_t)out_end_i[e] + len2;
 		max2 = std::max(max2, len2);
 	}
-	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t b8 = al((size_t)(n + 1) * 8), b4 = al((size_t)n * 4), bst = al((size_t)n * 32);
-	const int64_t dcap = std::min<int64_t>(cigar_cap, ops_bytes);   /* (a list has no more runs than ops) */
-	int rc = grow(h, &h->d_out, &h->out_bytes, 3 * b8 + 8 * b4);
-	if (rc) return rc;
-	rc = grow(h, &h->d_order, &h->order_bytes, (size_t)ops_bytes + 256);
-	if (rc) return rc;
-	rc = grow(h, &h->d_cg, &h->cg_bytes, 2 * b4 + bst + b8 + al((size_t)dcap * 4) + 256);
-	if (rc) return rc;
-	char *dw = (char *)h->d_out, *dc = (char *)h->d_cg, *dl = (char *)h->d_str;
-	int64_t *d_woff1 = (int64_t *)dw, *d_woff2 = (int64_t *)(dw + b8), *d_ops_off = (int64_t *)(dw + 2 * b8);
-	int32_t *d4[8];
-	for (int x = 0; x < 8; ++x) d4[x] = (int32_t *)(dw + 3 * b8 + (size_t)x * b4);
-	int32_t *d_len1 = d4[0], *d_len2 = d4[1], *d_ws = d4[2], *d_sc = d4[3], *d_ei = d4[4], *d_ej = d4[5], *d_st = d4[6], *d_nops = d4[7];
-	int32_t *d_ncigar = (int32_t *)dc, *d_ncout = (int32_t *)(dc + b4), *d_stats = (int32_t *)(dc + 2 * b4);
-	int64_t *d_coff = (int64_t *)(dc + 2 * b4 + bst);
-	uint32_t *d_cigar = (uint32_t *)(dc + 2 * b4 + bst + b8);
-	int *d_bad = (int *)(dc + 2 * b4 + bst + b8 + al((size_t)dcap * 4));
-	uint8_t *d_ops = (uint8_t *)h->d_order;
+	const int64_t dcap = std::min<int64_t>(co.cap, ops_bytes);   /* (a list has no more runs than ops) */
+	char bad_text[256];
+	snprintf(bad_text, sizeof bad_text, "%s: a hit's window does not reproduce its score and end column (target columns [ws, j*) of at most %d)", who, max2);
 	hipStream_t s = h->stream;
-	HIP_TRY(h, hipMemcpyAsync(d_ops_off, slot.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemsetAsync(d_bad, 0, 4, s));
+	WindowBufs w;
+	int rc = window_carve(h, n, dcap, 0, false, true, &h->d_order, &h->order_bytes, (size_t)ops_bytes + 256, w);
+	if (rc) return rc;
+	HIP_TRY(h, hipMemcpyAsync(w.ops_off, slot.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemsetAsync(w.bad, 0, 4, s));
 	at::ScanWindowArgs wa;
 	memset(&wa, 0, sizeof wa);
-	wa.n = n; wa.k = k; wa.nq = (int)nq; wa.enc = enc; wa.nrev0 = (int)(nq + nt);
-	wa.lkey = (const unsigned long long *)dl; wa.lej = (const int *)(dl + bkey + bl4); wa.eq = d_eq;
+	wa.n = n; wa.k = k; wa.nq = (int)nq; wa.enc = strands != AT_STRAND_FWD; wa.nrev0 = (int)(nq + nt);
+	wa.lkey = lb.key; wa.lej = lb.ej; wa.eq = anchor ? lb.ei : nullptr;
 	wa.swoff = (const long long *)rs.d_swoff; wa.slen = rs.d_len;
-	wa.woff1 = (long long *)d_woff1; wa.woff2 = (long long *)d_woff2; wa.len1 = d_len1; wa.len2 = d_len2; wa.ws = d_ws;
-	wa.w_score = d_sc; wa.w_end_j = d_ej; wa.ncigar = d_ncigar; wa.stats = d_stats; wa.ncigar_out = d_ncout; wa.bad = d_bad;
+	wa.woff1 = (long long *)w.woff1; wa.woff2 = (long long *)w.woff2; wa.len1 = w.len1; wa.len2 = w.len2; wa.ws = w.aux;
+	wa.w_score = w.sc; wa.w_end_j = w.ej; wa.ncigar = w.ncigar; wa.stats = w.stats; wa.ncigar_out = w.ncout; wa.bad = w.bad;
 	HIP_TRY(h, at_scan_window_launch(&wa, h->ncu, s));
 	const std::string cfg0 = h->cfg;
 	{
 		/* the window pass is an infix batch with op lists whatever the handle's settings say; they are put back at once */
 		const int keep_infix = h->edit_infix, keep_tb = h->edit_tb;
 		h->edit_infix = 1; h->edit_tb = 1; h->infix_anchor = anchor;
-		rc = align_device(h, AT_MODE_EDIT, n, rs.d_words, 2, d_woff1, d_len1, d_woff2, d_len2, maxq, max2, 0, 1, d_sc, d_ei, d_ej, d_st,
-		                  d_ops, d_ops_off, d_nops, s, 0, 0);
+		rc = align_device(h, AT_MODE_EDIT, n, rs.d_words, 2, w.woff1, w.len1, w.woff2, w.len2, maxq, max2, 0, 1, w.sc, w.ei, w.ej, w.st,
+		                  w.ops, w.ops_off, w.nops, s, 0, 0);
 		h->edit_infix = keep_infix; h->edit_tb = keep_tb; h->infix_anchor = 0;
 	}
 	if (rc) { (void)hipStreamSynchronize(s); return rc; }
 	const std::string cfg1 = h->cfg;
-	rc = at_cigar_batch_device(h, n, rs.d_words, 2, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_ops_off, d_nops, flags, d_ncigar, d_stats, d_coff,
-	                           d_cigar, dcap, s);
+	rc = at_cigar_batch_device(h, n, rs.d_words, 2, w.woff1, w.woff2, w.ei, w.ej, w.ops, w.ops_off, w.nops, flags, w.ncigar, w.stats, w.coff, w.cigar, dcap, s);
 	if (rc) { (void)hipStreamSynchronize(s); return rc; }
 	HIP_TRY(h, at_scan_check_launch(&wa, h->ncu, s));
-	int bad = 0;
-	HIP_TRY(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipMemcpyAsync(out_ncigar, d_ncout, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipMemcpyAsync(out_stats, d_stats, (size_t)n * 32, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipMemcpyAsync(out_cigar_off, d_coff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipStreamSynchronize(s));
-	if (bad) return fail(h, AT_ERR_RANGE, "%s: a hit's window does not reproduce its score and end column (target columns [ws, j*) of at most %d)", who, max2);
-	/* the words of the entries that end within the caller's capacity: a prefix of the device buffer */
-	int64_t fit = 0;
-	for (int64_t e = 0; e < n; ++e) if (out_cigar_off[e + 1] <= cigar_cap) fit = out_cigar_off[e + 1]; else break;
-	if (fit > 0) {
-		HIP_TRY(h, hipMemcpyAsync(out_cigar, d_cigar, (size_t)fit * 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(h, hipStreamSynchronize(s));
-	}
+	if ((rc = window_fetch(h, w, n, bad_text, co.ncigar, co.stats, co.off)) || (rc = window_words(h, w, co.off, n, co.cap, co.words))) return rc;
 	snprintf(h->cfg, sizeof h->cfg, "%.300s; windows: %.200s, cigars: %d lanes/pair", cfg0.c_str(), cfg1.c_str(), h->last_cigar_lanes);
 	return AT_OK;
 }
@@ -2738,70 +2810,38 @@ extern "C" int at_scan(at_handle *h,
                        int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
                        uint32_t *out_cigar, int64_t cigar_cap)
 {
+	const char *who = "at_scan";
 	if (!h) return fail(nullptr, AT_ERR_ARG, "at_scan: NULL handle");
-	if (nq < 0 || nt < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "at_scan: negative size");
-	if (k < 1 || k > 64) return fail(h, AT_ERR_ARG, "at_scan: k = %d outside 1..64", k);
-	if (strands < AT_STRAND_FWD || strands > AT_STRAND_BOTH) return fail(h, AT_ERR_ARG, "at_scan: strands = %d outside 1..3", strands);
-	if (tile_cols < 0 || (tile_cols & 15))
-		return fail(h, AT_ERR_ARG, "at_scan: tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)", tile_cols, at::kScanDefaultTile);
-	if (flags & ~AT_CIGAR_M) return fail(h, AT_ERR_ARG, "at_scan: flags = %d (AT_CIGAR_M or 0)", flags);
+	const QuerySets qt = {nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len};
+	const ListOut out = {out_target, out_score, out_end_i, out_end_j, out_state, out_strand, out_nhits};
+	const CigarOut co = {out_stats, out_ncigar, out_cigar_off, out_cigar, cigar_cap};
+	int rc = check_sizes(h, who, nq, nt, cigar_cap, k);
+	if (rc || (rc = check_options(h, who, strands, tile_cols, at::kScanDefaultTile, flags, co, nq, nt)) || (rc = check_one_gpu(h, who))) return rc;
 	const bool rev = strands != AT_STRAND_FWD;
-	const bool cg = out_stats || out_ncigar || out_cigar_off || out_cigar;
-	if (cg && (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)))
-		return fail(h, AT_ERR_ARG, "at_scan: the CIGAR outputs are either all NULL or all given");
-	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "at_scan: %lld queries + %lld targets: at most 2^31 - 1 reads", (long long)nq, (long long)nt);
-	if (rev && (nt >= (1LL << 30) || 2 * nq + nt >= (1LL << 31)))
-		return fail(h, AT_ERR_ARG, "at_scan: %lld queries, %lld targets: a reverse strand needs nt < 2^30 and 2 nq + nt < 2^31", (long long)nq, (long long)nt);
-	if (h->comm) return fail(h, AT_ERR_DOMAIN, "at_scan: one GPU only (this handle belongs to a multi-process job)");
 	if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "at_scan needs the unit mismatch cost: u = %d, not 1", h->u);
 	if (nq == 0) return AT_OK;
-	if (!q_blob || !q_off || !q_len || !out_target || !out_score || !out_end_i || !out_end_j || !out_state || !out_nhits ||
-	    (rev && !out_strand) || (nt > 0 && (!t_blob || !t_off || !t_len)))
-		return fail(h, AT_ERR_ARG, "at_scan: NULL argument");
+	if ((rc = check_list_pointers(h, who, qt, out, rev))) return rc;
 	int32_t maxq = 0;
 	for (int64_t q = 0; q < nq; ++q) {
-		if (q_len[q] < 0 || q_off[q] < 0) return fail(h, AT_ERR_ARG, "query %lld: negative length or offset", (long long)q);
+		if ((rc = check_read(h, "query", q, q_len[q], q_off[q], false))) return rc;
 		if (q_len[q] > at::kScanMaxQuery) return fail(h, AT_ERR_DOMAIN, "at_scan: query %lld has %d bases, more than %d", (long long)q, q_len[q], at::kScanMaxQuery);
 		maxq = std::max(maxq, q_len[q]);
 	}
-	for (int64_t t = 0; t < nt; ++t)
-		if (t_len[t] < 0 || t_off[t] < 0) return fail(h, AT_ERR_ARG, "target %lld: negative length or offset", (long long)t);
+	for (int64_t t = 0; t < nt; ++t) if ((rc = check_read(h, "target", t, t_len[t], t_off[t], false))) return rc;
 	const int32_t tile = tile_cols > 0 ? tile_cols : at::kScanDefaultTile;
-	return guarded(h, "at_scan", [&]() -> int {
-		for (int64_t e = 0; e < nq * k; ++e) { out_target[e] = -1; out_score[e] = 0; out_end_i[e] = 0; out_end_j[e] = 0; out_state[e] = 0; }
-		if (out_strand) for (int64_t e = 0; e < nq * k; ++e) out_strand[e] = -1;
-		for (int64_t q = 0; q < nq; ++q) out_nhits[q] = 0;
-		if (cg) {
-			for (int64_t e = 0; e < nq * k; ++e) { out_ncigar[e] = 0; for (int x = 0; x < 8; ++x) out_stats[e * 8 + x] = -1; }
-			for (int64_t e = 0; e <= nq * k; ++e) out_cigar_off[e] = 0;
-		}
+	return guarded(h, who, [&]() -> int {
+		list_out_init(out, nq, k, co);
 		if (nt == 0) {
 			snprintf(h->cfg, sizeof h->cfg, "scan: tile=%d overlap<=0 groups=0 k=%d strands=%s, 0 blocks, 0 slices; ", tile, k, scan_strands_text(strands));
 			return (int)AT_OK;
 		}
-		int64_t bytes = 0;
-		for (int64_t q = 0; q < nq; ++q) bytes += q_len[q];
-		for (int64_t t = 0; t < nt; ++t) bytes += t_len[t];
-		std::vector<uint8_t> blob((size_t)bytes + 32);
-		std::vector<int64_t> off((size_t)(nq + nt));
-		std::vector<int32_t> len((size_t)(nq + nt));
-		int64_t at = 0;
-		for (int64_t r = 0; r < nq + nt; ++r) {
-			const bool isq = r < nq;
-			const int32_t l = isq ? q_len[r] : t_len[r - nq];
-			if (l) memcpy(blob.data() + at, isq ? q_blob + q_off[r] : t_blob + t_off[r - nq], (size_t)l);
-			off[(size_t)r] = at; len[(size_t)r] = l; at += l;
-		}
 		ReadSet rs;
-		int rc = upload_reads(h, AT_MODE_EDIT, nq + nt, blob.data(), off.data(), len.data(), &rs, rev ? nq : 0);
-		if (rc) return rc;
+		int rc2 = upload_sets(h, AT_MODE_EDIT, qt, rev, &rs);
+		if (rc2) return rc2;
 		if (rs.bits != 2) return fail(h, AT_ERR_DOMAIN, "at_scan needs 2-bit reads: some base of a query or a target is not one of ACGT");
-		size_t bkey = 0, bl4 = 0;
-		rc = scan_lists(h, nq, q_len, nt, t_len, rs, k, use_cutoff, cutoff, strands, tile, out_target, out_score, out_end_i, out_end_j, out_state,
-		                out_strand, out_nhits, &bkey, &bl4);
-		if (rc || !cg) return rc;
-		return scan_cigars(h, nq, k, strands, rs, nt, maxq, bkey, bl4, out_target, out_score, out_end_i, out_end_j, flags, out_stats, out_ncigar,
-		                   out_cigar_off, out_cigar, cigar_cap);
+		ListBufs lb;
+		if ((rc2 = scan_lists(h, qt, rs, k, use_cutoff, cutoff, strands, tile, out, lb)) || !co.any()) return rc2;
+		return scan_cigars(h, nq, k, strands, rs, nt, maxq, lb, out_target, out_score, out_end_i, out_end_j, flags, co);
 	});
 }
 
@@ -2835,73 +2875,46 @@ extern "C" int64_t at_scan_local_window(int32_t end_i, int64_t end_j, int32_t sc
  * shape, a uniform batch, and the shorter ones at the targets' ends) and each pass in SLICES of at most `chunk` tile pairs:
  * descriptors, the batch entry's sweep, fold.  Behind the last slice the run's slots are unpacked and merged.  The lists stay in
  * h->d_str behind the call. */
-static int localscan_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64_t nt, const int32_t *t_len, const ReadSet &rs,
-                           int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile, int32_t *out_target, int32_t *out_score,
-                           int32_t *out_end_i, int32_t *out_end_j, int32_t *out_state, int32_t *out_strand, int32_t *out_nhits,
-                           size_t *list_bkey, size_t *list_b4)
+static int localscan_lists(at_handle *h, const QuerySets &qt, const ReadSet &rs, int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile,
+                           const ListOut &out, ListBufs &lb)
 {
-	const int enc = strands != AT_STRAND_FWD, two = strands == AT_STRAND_BOTH;
-	const int64_t nv = nq << two;
-	std::vector<int> qs((size_t)nq), qperm((size_t)nv), tperm((size_t)nt);
-	for (int64_t q = 0; q < nq; ++q) qs[(size_t)q] = (int)q;
-	for (int64_t t = 0; t < nt; ++t) tperm[(size_t)t] = (int)t;
-	std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
-	for (int64_t q = 0; q < nq; ++q) {
-		const int c = qs[(size_t)q];
-		if (two) { qperm[(size_t)(2 * q)] = c << 1; qperm[(size_t)(2 * q + 1)] = (c << 1) | 1; }
-		else qperm[(size_t)q] = enc ? (c << 1) | 1 : c;
-	}
-	struct Block { int qa, nqb; int32_t l1; };
-	std::vector<Block> blocks;
+	const int64_t nq = qt.nq, nt = qt.nt;
+	const int32_t *t_len = qt.t_len;
+	const at::QueryOrder qo = at::query_order(nq, qt.q_len, strands);
+	std::vector<int> tperm((size_t)nt);
+	std::iota(tperm.begin(), tperm.end(), 0);
 	int64_t most = 0;
-	for (int64_t a = 0, b; a < nq; a = b) {
-		const int32_t L = q_len[qs[(size_t)a]];
-		for (b = a; b < nq && q_len[qs[(size_t)b]] == L; ++b) {}
-		blocks.push_back({(int)(a << two), (int)((b - a) << two), L});
-		most = std::max<int64_t>(most, ((b - a) << two) * nt);
-	}
+	for (const at::QueryBlock &B : qo.blocks) most = std::max<int64_t>(most, (int64_t)B.nqb * nt);
 	int32_t maxt = 0;
 	for (int64_t t = 0; t < nt; ++t) maxt = std::max(maxt, t_len[t]);
-	/* a slice holds tile pairs: a run has at least as many tiles as pairs, so the bound of the largest block's tiles is not known here */
-	int64_t chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
-	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, 1LL << 28));
-	{
-		const int64_t most_tiles = most * std::max<int64_t>(1, at::localscan_tiles(maxt, tile));   /* (an upper bound: some are not swept) */
-		chunk = std::min<int64_t>(chunk, std::max<int64_t>(most_tiles, 1));
-	}
-	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t b8 = al((size_t)chunk * 8), b4 = al((size_t)chunk * 4), bq = al((size_t)nv * 4), bt = al((size_t)nt * 4), bg = al(((size_t)nt + 1) * 8);
-	const size_t nl = (size_t)nq * (size_t)k, bkey = al(nl * 8), bl4 = al(nl * 4);
-	int rc = grow(h, &h->d_desc, &h->desc_bytes, 5 * b8 + 2 * b4 + 2 * bg + bq + bt);
+	/* a slice holds tile pairs: a run has at least as many tiles as pairs; its bound is that of the largest block's tiles (an upper bound:
+	 * some are not swept) */
+	const int64_t chunk = at::slice_clamp(env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault), most * std::max<int64_t>(1, at::localscan_tiles(maxt, tile)));
+	int64_t *d_woff1 = nullptr, *d_woff2 = nullptr; long long *d_s0 = nullptr, *d_slot = nullptr, *d_tpre[2]; unsigned long long *d_pkey = nullptr;
+	int32_t *d_len1 = nullptr, *d_len2 = nullptr, *d_r[8]; int *d_qperm = nullptr, *d_tperm = nullptr;
+	int rc = carve(h, &h->d_desc, &h->desc_bytes, [&](Carver &c) {
+		d_woff1 = c.take<int64_t>((size_t)chunk); d_woff2 = c.take<int64_t>((size_t)chunk);
+		d_s0 = c.take<long long>((size_t)chunk); d_slot = c.take<long long>((size_t)chunk);
+		d_pkey = c.take<unsigned long long>((size_t)chunk);
+		d_len1 = c.take<int32_t>((size_t)chunk); d_len2 = c.take<int32_t>((size_t)chunk);
+		for (long long *&x : d_tpre) x = c.take<long long>((size_t)nt + 1);
+		d_qperm = c.take<int>((size_t)qo.nv); d_tperm = c.take<int>((size_t)nt);
+	});
+	if (!rc) rc = carve(h, &h->d_out, &h->out_bytes, [&](Carver &c) { for (int32_t *&x : d_r) x = c.take<int32_t>((size_t)chunk); });
+	if (!rc) rc = list_bufs(h, (size_t)nq * (size_t)k, true, &lb);
 	if (rc) return rc;
-	rc = grow(h, &h->d_out, &h->out_bytes, 8 * b4);
-	if (rc) return rc;
-	const size_t lbytes = bkey + 3 * bl4 + 256;
-	rc = grow(h, &h->d_str, &h->str_bytes, lbytes);
-	if (rc) return rc;
-	char *dd = (char *)h->d_desc, *dr = (char *)h->d_out, *dl = (char *)h->d_str;
-	int64_t *d_woff1 = (int64_t *)dd, *d_woff2 = (int64_t *)(dd + b8);
-	long long *d_s0 = (long long *)(dd + 2 * b8), *d_slot = (long long *)(dd + 3 * b8);
-	unsigned long long *d_pkey = (unsigned long long *)(dd + 4 * b8);
-	int32_t *d_len1 = (int32_t *)(dd + 5 * b8), *d_len2 = (int32_t *)(dd + 5 * b8 + b4);
-	long long *d_tpre[2] = {(long long *)(dd + 5 * b8 + 2 * b4), (long long *)(dd + 5 * b8 + 2 * b4 + bg)};
-	int *d_qperm = (int *)(dd + 5 * b8 + 2 * b4 + 2 * bg), *d_tperm = (int *)(dd + 5 * b8 + 2 * b4 + 2 * bg + bq);
-	int32_t *d_r[8];
-	for (int x = 0; x < 8; ++x) d_r[x] = (int32_t *)(dr + (size_t)x * b4);
-	unsigned long long *d_key = (unsigned long long *)dl;
-	int *d_lei = (int *)(dl + bkey), *d_lej = (int *)(dl + bkey + bl4), *d_lst = (int *)(dl + bkey + 2 * bl4), *d_bad = (int *)(dl + bkey + 3 * bl4);
 	hipStream_t s = h->stream;
-	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nv * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_qperm, qo.qperm.data(), (size_t)qo.nv * 4, hipMemcpyHostToDevice, s));
 	HIP_TRY(h, hipMemcpyAsync(d_tperm, tperm.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemsetAsync(dl, 0, lbytes, s));
+	HIP_TRY(h, hipMemsetAsync(lb.key, 0, lb.lbytes, s));
 	std::string cfg0;
 	int64_t nslices = 0, tiles_all = 0, ov_most = 0;
-	struct Ev { hipEvent_t e[2] = {nullptr, nullptr}; ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
-	for (hipEvent_t &x : ev.e) HIP_TRY(h, hipEventCreate(&x));
+	StreamEvents ev;
+	if ((rc = ev.create(h, 2))) return rc;
 	HIP_TRY(h, hipEventRecord(ev.e[0], s));
 	std::vector<long long> tpre[2];
 	for (auto &v : tpre) v.assign((size_t)nt + 1, 0);
-	for (const Block &B : blocks) {
+	for (const at::QueryBlock &B : qo.blocks) {
 		/* the overlap depends on the query length: the block's prefix arrays of full and of shorter tiles per target */
 		const int64_t ov = at::localscan_overlap(B.l1, use_cutoff, cutoff, h->m, h->u, h->o, h->e);
 		{
@@ -2935,11 +2948,11 @@ static int localscan_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64
 			at::LocalScanArgs sa;
 			memset(&sa, 0, sizeof sa);
 			sa.cap = chunk; sa.p0 = p0; sa.npairs = n; sa.ntb = nt;
-			sa.qa = B.qa; sa.nq = (int)nq; sa.enc = enc; sa.nrev0 = (int)(nq + nt); sa.bpw = rs.bits == 2 ? 16 : 4; sa.qperm = d_qperm;
+			sa.qa = B.qa; sa.nq = (int)nq; sa.enc = qo.enc; sa.nrev0 = (int)(nq + nt); sa.bpw = rs.bits == 2 ? 16 : 4; sa.qperm = d_qperm;
 			sa.swoff = (const long long *)rs.d_swoff; sa.slen = rs.d_len; sa.tile = tile; sa.overlap = ov;
 			sa.woff1 = (long long *)d_woff1; sa.woff2 = (long long *)d_woff2; sa.len1 = d_len1; sa.len2 = d_len2; sa.s0 = d_s0; sa.slot = d_slot;
 			sa.score = d_r[0]; sa.end_i = d_r[1]; sa.end_j = d_r[2];
-			sa.key = d_pkey; sa.bad = d_bad;
+			sa.key = d_pkey; sa.bad = lb.bad;
 			sa.o_score = d_r[4]; sa.o_end_i = d_r[5]; sa.o_end_j = d_r[6]; sa.o_state = d_r[7];
 			HIP_TRY(h, at_localscan_init_launch(&sa, h->ncu, s));
 			for (int pass = 0; pass < 2; ++pass) {
@@ -2960,47 +2973,16 @@ static int localscan_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64
 				}
 			}
 			HIP_TRY(h, at_localscan_unpack_launch(&sa, h->ncu, s));
-			at::SearchMergeArgs ma;
-			memset(&ma, 0, sizeof ma);
-			ma.s0 = p0; ma.n = n; ma.ntb = nt; ma.qa = B.qa; ma.ta = 0;
-			ma.enc = enc; ma.two = two;
-			ma.nqs = (int)((p0 + n - 1) / (nt << two) - p0 / (nt << two) + 1);
-			ma.qperm = d_qperm; ma.tperm = d_tperm;
-			ma.score = d_r[4]; ma.end_i = d_r[5]; ma.end_j = d_r[6]; ma.state = d_r[7];
-			ma.k = k; ma.is_edit = 0; ma.use_cutoff = use_cutoff ? 1 : 0; ma.cutoff = cutoff;
-			ma.lkey = d_key; ma.lei = d_lei; ma.lej = d_lej; ma.lst = d_lst; ma.bad = d_bad;
-			HIP_TRY(h, at_search_merge_launch(&ma, s));
+			if ((rc = merge_slice(h, qo, lb, d_qperm, d_tperm, d_r + 4, p0, n, nt, B.qa, 0, k, 0, use_cutoff, cutoff))) return rc;
 		}
 	}
 	HIP_TRY(h, hipEventRecord(ev.e[1], s));
-	std::vector<char> hl(lbytes);
-	HIP_TRY(h, hipMemcpyAsync(hl.data(), dl, lbytes, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipStreamSynchronize(s));
+	if ((rc = lists_readback(h, lb, nq, k, qo.enc, false, "at_scan_local", out))) return rc;
 	float sweep_ms = 0.f;
 	HIP_TRY(h, hipEventElapsedTime(&sweep_ms, ev.e[0], ev.e[1]));
-	int bad = 0;
-	memcpy(&bad, hl.data() + bkey + 3 * bl4, 4);
-	if (bad) return fail(h, AT_ERR_DOMAIN, "at_scan_local: a pair outside the domain on which the reference is defined");
-	const unsigned long long *hk = (const unsigned long long *)hl.data();
-	const int32_t *hei = (const int32_t *)(hl.data() + bkey), *hej = (const int32_t *)(hl.data() + bkey + bl4), *hst = (const int32_t *)(hl.data() + bkey + 2 * bl4);
-	for (int64_t q = 0; q < nq; ++q) {
-		int nh = 0;
-		for (int j = 0; j < k; ++j) {
-			const size_t e = (size_t)q * k + j;
-			if (!hk[e]) break;
-			const uint32_t low = ~(uint32_t)hk[e];
-			out_target[e] = (int32_t)(low >> enc);
-			if (out_strand) out_strand[e] = enc ? (int32_t)(low & 1u) : 0;
-			out_score[e] = (int32_t)((uint32_t)(hk[e] >> 32) ^ 0x80000000u);
-			out_end_i[e] = hei[e]; out_end_j[e] = hej[e]; out_state[e] = hst[e];
-			++nh;
-		}
-		out_nhits[q] = nh;
-	}
 	/* (the sweep phase's device time as scan_lists reports it: tools/local_scan_rate.py; at most 360 bytes, which localscan_cigars keeps whole) */
 	snprintf(h->cfg, sizeof h->cfg, "local-scan: tile=%d overlap<=%lld tiles=%lld k=%d strands=%s, %lld blocks, %lld slices; %.200s sweep=%.3fms", tile,
-	         (long long)ov_most, (long long)tiles_all, k, scan_strands_text(strands), (long long)blocks.size(), (long long)nslices, cfg0.c_str(), (double)sweep_ms);
-	*list_bkey = bkey; *list_b4 = bl4;
+	         (long long)ov_most, (long long)tiles_all, k, scan_strands_text(strands), (long long)qo.blocks.size(), (long long)nslices, cfg0.c_str(), (double)sweep_ms);
 	return AT_OK;
 }
 
@@ -3008,11 +2990,10 @@ static int localscan_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64
  * tracebacks and the CIGAR kernels (at_localscan.hip.h), in pieces of at most 2^20 hits or 1 GB of op slots (3.13's bounds) and no
  * more hits than a slice has pairs (AT_ALLPAIRS_CHUNK: the tests' 1 and 7 make pieces of 1 and 7 hits).  Unused entries keep what the entry gave them: 0 runs, a row of
  * -1 and no room in out_cigar */
-static int localscan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadSet &rs, int64_t nt, int32_t maxq, size_t bkey, size_t bl4,
+static int localscan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadSet &rs, int64_t nt, int32_t maxq, const ListBufs &lb,
                             const int32_t *out_target, const int32_t *out_score, const int32_t *out_end_i, const int32_t *out_end_j, int flags,
-                            int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap)
+                            const CigarOut &co)
 {
-	const int enc = strands != AT_STRAND_FWD;
 	const int64_t nlist = nq * k;
 	std::vector<long long> used;
 	std::vector<int32_t> wlen;
@@ -3022,94 +3003,66 @@ static int localscan_cigars(at_handle *h, int64_t nq, int k, int strands, const 
 		wlen.push_back((int32_t)(out_end_j[e] - at::localscan_window_start(out_end_j[e], out_end_i[e], out_score[e], h->m, h->u, h->o, h->e)));
 	}
 	const int64_t nused = (int64_t)used.size();
-	const int64_t piece_hits = std::max<long long>(1, std::min<long long>(env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20), 1LL << 20));
-	const int64_t piece_ops = 1LL << 30;
-	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+	const int64_t piece_hits = std::max<long long>(1, std::min<long long>(env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault), 1LL << 20)), piece_ops = 1LL << 30;
 	hipStream_t s = h->stream;
-	char *dl = (char *)h->d_str;
 	const std::string cfg0 = h->cfg;
 	std::string cfg1;
 	int64_t words_total = 0, npieces = 0;   /* CIGAR words of the hits so far: the next piece's place in out_cigar */
 	bool fits = true;                        /* every entry so far ends within the caller's capacity */
 	int64_t next_entry = 0;                  /* out_cigar_off is complete up to here */
 	for (int64_t a0 = 0; a0 < nused; ) {
-		int64_t n = 0, ops_bytes = 0;
+		int64_t ops_bytes = 0;
+		const int64_t n = at::piece_end(a0, nused, piece_hits, piece_ops, [&](int64_t x) { return (int64_t)maxq + wlen[(size_t)x]; }, &ops_bytes) - a0;
 		int32_t max2 = 1;
-		std::vector<int64_t> slot;
-		while (a0 + n < nused && n < piece_hits) {
-			const int64_t need = (int64_t)maxq + wlen[(size_t)(a0 + n)];
-			if (n > 0 && ops_bytes + need > piece_ops) break;
-			slot.push_back(ops_bytes);
-			ops_bytes += need;
-			max2 = std::max(max2, wlen[(size_t)(a0 + n)]);
-			++n;
+		std::vector<int64_t> slot((size_t)n);
+		for (int64_t x = 0, at = 0; x < n; at += (int64_t)maxq + wlen[(size_t)(a0 + x)], ++x) {
+			slot[(size_t)x] = at;
+			max2 = std::max(max2, wlen[(size_t)(a0 + x)]);
 		}
-		const size_t b8 = al((size_t)(n + 1) * 8), b4 = al((size_t)n * 4), bst = al((size_t)n * 32);
-		const int64_t dcap = std::min<int64_t>(std::max<int64_t>(cigar_cap - words_total, 0), ops_bytes);   /* (a list has no more runs than ops) */
-		int rc = grow(h, &h->d_out, &h->out_bytes, 4 * b8 + 8 * b4);
-		if (rc) return rc;
-		rc = grow(h, &h->d_order, &h->order_bytes, (size_t)ops_bytes + 256);
-		if (rc) return rc;
-		rc = grow(h, &h->d_cg, &h->cg_bytes, b4 + bst + b8 + al((size_t)dcap * 4) + 256);
-		if (rc) return rc;
-		char *dw = (char *)h->d_out, *dc = (char *)h->d_cg;
-		int64_t *d_woff1 = (int64_t *)dw, *d_woff2 = (int64_t *)(dw + b8), *d_ops_off = (int64_t *)(dw + 2 * b8);
-		long long *d_eidx = (long long *)(dw + 3 * b8);
-		int32_t *d4[8];
-		for (int x = 0; x < 8; ++x) d4[x] = (int32_t *)(dw + 4 * b8 + (size_t)x * b4);
-		int32_t *d_len1 = d4[0], *d_len2 = d4[1], *d_ws = d4[2], *d_sc = d4[3], *d_ei = d4[4], *d_ej = d4[5], *d_st = d4[6], *d_nops = d4[7];
-		int32_t *d_ncigar = (int32_t *)dc, *d_stats = (int32_t *)(dc + b4);
-		int64_t *d_coff = (int64_t *)(dc + b4 + bst);
-		uint32_t *d_cigar = (uint32_t *)(dc + b4 + bst + b8);
-		int *d_bad = (int *)(dc + b4 + bst + b8 + al((size_t)dcap * 4));
-		uint8_t *d_ops = (uint8_t *)h->d_order;
-		HIP_TRY(h, hipMemcpyAsync(d_ops_off, slot.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-		HIP_TRY(h, hipMemcpyAsync(d_eidx, used.data() + a0, (size_t)n * 8, hipMemcpyHostToDevice, s));
-		HIP_TRY(h, hipMemsetAsync(d_bad, 0, 4, s));
-		at::LocalScanWindowArgs wa;
-		memset(&wa, 0, sizeof wa);
-		wa.n = n; wa.nlist = nlist; wa.eidx = d_eidx; wa.k = k; wa.nq = (int)nq; wa.enc = enc; wa.nrev0 = (int)(nq + nt); wa.bpw = rs.bits == 2 ? 16 : 4;
-		wa.m = h->m; wa.u = h->u; wa.o = h->o; wa.e = h->e;
-		wa.lkey = (const unsigned long long *)dl; wa.lei = (const int *)(dl + bkey); wa.lej = (const int *)(dl + bkey + bl4);
-		wa.swoff = (const long long *)rs.d_swoff; wa.slen = rs.d_len;
-		wa.woff1 = (long long *)d_woff1; wa.woff2 = (long long *)d_woff2; wa.len1 = d_len1; wa.len2 = d_len2; wa.ws = d_ws;
-		wa.w_score = d_sc; wa.w_end_i = d_ei; wa.w_end_j = d_ej; wa.ncigar = d_ncigar; wa.stats = d_stats; wa.bad = d_bad;
-		HIP_TRY(h, at_localscan_window_launch(&wa, h->ncu, s));
-		rc = align_device(h, AT_MODE_LOCAL, n, rs.d_words, rs.bits, d_woff1, d_len1, d_woff2, d_len2, maxq, max2, 0, 1, d_sc, d_ei, d_ej, d_st,
-		                  d_ops, d_ops_off, d_nops, s, 0, 0);
-		if (rc) { (void)hipStreamSynchronize(s); return rc; }
-		if (cfg1.empty()) cfg1 = h->cfg;
-		rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_ops_off, d_nops, flags, d_ncigar, d_stats, d_coff,
-		                           d_cigar, dcap, s);
-		if (rc) { (void)hipStreamSynchronize(s); return rc; }
-		HIP_TRY(h, at_localscan_check_launch(&wa, h->ncu, s));
-		int bad = 0;
+		const int64_t dcap = std::min<int64_t>(std::max<int64_t>(co.cap - words_total, 0), ops_bytes);   /* (a list has no more runs than ops) */
+		char bad_text[256];
+		snprintf(bad_text, sizeof bad_text, "at_scan_local: a hit's window does not reproduce its score and end cell (target columns (ws, j*] of at most %d)", max2);
 		std::vector<int32_t> hnc((size_t)n), hst((size_t)n * 8);
 		std::vector<int64_t> hco((size_t)n + 1);
-		HIP_TRY(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(h, hipMemcpyAsync(hnc.data(), d_ncigar, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(h, hipMemcpyAsync(hst.data(), d_stats, (size_t)n * 32, hipMemcpyDeviceToHost, s));
-		HIP_TRY(h, hipMemcpyAsync(hco.data(), d_coff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-		HIP_TRY(h, hipStreamSynchronize(s));
-		if (bad) return fail(h, AT_ERR_RANGE, "at_scan_local: a hit's window does not reproduce its score and end cell (target columns (ws, j*] of at most %d)", max2);
-		/* the piece's words that end within the caller's capacity: a prefix of the device buffer, behind the pieces before it */
-		int64_t fit = 0;
+		WindowBufs w;
+		int rc = window_carve(h, n, dcap, 0, true, false, &h->d_order, &h->order_bytes, (size_t)ops_bytes + 256, w);
+		if (rc) return rc;
+		HIP_TRY(h, hipMemcpyAsync(w.ops_off, slot.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+		HIP_TRY(h, hipMemcpyAsync(w.eidx, used.data() + a0, (size_t)n * 8, hipMemcpyHostToDevice, s));
+		HIP_TRY(h, hipMemsetAsync(w.bad, 0, 4, s));
+		at::LocalScanWindowArgs wa;
+		memset(&wa, 0, sizeof wa);
+		wa.n = n; wa.nlist = nlist; wa.eidx = w.eidx; wa.k = k; wa.nq = (int)nq; wa.enc = strands != AT_STRAND_FWD; wa.nrev0 = (int)(nq + nt);
+		wa.bpw = rs.bits == 2 ? 16 : 4;
+		wa.m = h->m; wa.u = h->u; wa.o = h->o; wa.e = h->e;
+		wa.lkey = lb.key; wa.lei = lb.ei; wa.lej = lb.ej;
+		wa.swoff = (const long long *)rs.d_swoff; wa.slen = rs.d_len;
+		wa.woff1 = (long long *)w.woff1; wa.woff2 = (long long *)w.woff2; wa.len1 = w.len1; wa.len2 = w.len2; wa.ws = w.aux;
+		wa.w_score = w.sc; wa.w_end_i = w.ei; wa.w_end_j = w.ej; wa.ncigar = w.ncigar; wa.stats = w.stats; wa.bad = w.bad;
+		HIP_TRY(h, at_localscan_window_launch(&wa, h->ncu, s));
+		rc = align_device(h, AT_MODE_LOCAL, n, rs.d_words, rs.bits, w.woff1, w.len1, w.woff2, w.len2, maxq, max2, 0, 1, w.sc, w.ei, w.ej, w.st,
+		                  w.ops, w.ops_off, w.nops, s, 0, 0);
+		if (rc) { (void)hipStreamSynchronize(s); return rc; }
+		if (cfg1.empty()) cfg1 = h->cfg;
+		rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, w.woff1, w.woff2, w.ei, w.ej, w.ops, w.ops_off, w.nops, flags, w.ncigar, w.stats, w.coff, w.cigar, dcap, s);
+		if (rc) { (void)hipStreamSynchronize(s); return rc; }
+		HIP_TRY(h, at_localscan_check_launch(&wa, h->ncu, s));
+		if ((rc = window_fetch(h, w, n, bad_text, hnc.data(), hst.data(), hco.data()))) return rc;
 		for (int64_t x = 0; x < n; ++x) {
 			const int64_t e = used[(size_t)(a0 + x)];
-			for (; next_entry <= e; ++next_entry) out_cigar_off[next_entry] = words_total + hco[(size_t)x];
-			out_ncigar[e] = hnc[(size_t)x];
-			memcpy(out_stats + e * 8, hst.data() + x * 8, 32);
-			if (fits && words_total + hco[(size_t)x + 1] <= cigar_cap) fit = hco[(size_t)x + 1]; else fits = false;
+			for (; next_entry <= e; ++next_entry) co.off[next_entry] = words_total + hco[(size_t)x];
+			co.ncigar[e] = hnc[(size_t)x];
+			memcpy(co.stats + e * 8, hst.data() + x * 8, 32);
 		}
-		if (fit > 0) {
-			HIP_TRY(h, hipMemcpyAsync(out_cigar + words_total, d_cigar, (size_t)fit * 4, hipMemcpyDeviceToHost, s));
-			HIP_TRY(h, hipStreamSynchronize(s));
-		}
+		/* the piece's words that end within the caller's capacity: a prefix of the device buffer, behind the pieces before it */
+		const int64_t room = fits ? co.cap - words_total : 0;
+		if ((rc = window_words(h, w, hco.data(), n, room, room > 0 ? co.words + words_total : nullptr))) return rc;
+		fits = fits && hco[(size_t)n] <= room;
 		words_total += hco[(size_t)n];
 		a0 += n;
 		++npieces;
 	}
-	for (; next_entry <= nlist; ++next_entry) out_cigar_off[next_entry] = words_total;
+	for (; next_entry <= nlist; ++next_entry) co.off[next_entry] = words_total;
 	snprintf(h->cfg, sizeof h->cfg, "%.360s; windows: %.180s, %lld pieces, cigars: %d lanes/pair", cfg0.c_str(), cfg1.c_str(), (long long)npieces, h->last_cigar_lanes);
 	return AT_OK;
 }
@@ -3123,75 +3076,40 @@ extern "C" int at_scan_local(at_handle *h,
                              int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
                              uint32_t *out_cigar, int64_t cigar_cap)
 {
+	const char *who = "at_scan_local";
 	if (!h) return fail(nullptr, AT_ERR_ARG, "at_scan_local: NULL handle");
-	if (nq < 0 || nt < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "at_scan_local: negative size");
-	if (k < 1 || k > 64) return fail(h, AT_ERR_ARG, "at_scan_local: k = %d outside 1..64", k);
-	if (strands < AT_STRAND_FWD || strands > AT_STRAND_BOTH) return fail(h, AT_ERR_ARG, "at_scan_local: strands = %d outside 1..3", strands);
-	if (tile_cols < 0 || (tile_cols & 15))
-		return fail(h, AT_ERR_ARG, "at_scan_local: tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)", tile_cols, at::kLocalScanDefaultTile);
-	if (flags & ~AT_CIGAR_M) return fail(h, AT_ERR_ARG, "at_scan_local: flags = %d (AT_CIGAR_M or 0)", flags);
+	const QuerySets qt = {nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len};
+	const ListOut out = {out_target, out_score, out_end_i, out_end_j, out_state, out_strand, out_nhits};
+	const CigarOut co = {out_stats, out_ncigar, out_cigar_off, out_cigar, cigar_cap};
+	int rc = check_sizes(h, who, nq, nt, cigar_cap, k);
+	if (rc || (rc = check_options(h, who, strands, tile_cols, at::kLocalScanDefaultTile, flags, co, nq, nt)) || (rc = check_one_gpu(h, who))) return rc;
 	const bool rev = strands != AT_STRAND_FWD;
-	const bool cg = out_stats || out_ncigar || out_cigar_off || out_cigar;
-	if (cg && (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)))
-		return fail(h, AT_ERR_ARG, "at_scan_local: the CIGAR outputs are either all NULL or all given");
-	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "at_scan_local: %lld queries + %lld targets: at most 2^31 - 1 reads", (long long)nq, (long long)nt);
-	if (rev && (nt >= (1LL << 30) || 2 * nq + nt >= (1LL << 31)))
-		return fail(h, AT_ERR_ARG, "at_scan_local: %lld queries, %lld targets: a reverse strand needs nt < 2^30 and 2 nq + nt < 2^31", (long long)nq, (long long)nt);
-	if (h->comm) return fail(h, AT_ERR_DOMAIN, "at_scan_local: one GPU only (this handle belongs to a multi-process job)");
 	if (at::localscan_scoring_ok(h->m, h->o, h->e) != AT_OK)
 		return fail(h, AT_ERR_DOMAIN, "at_scan_local needs m >= 1, o <= -1 and e <= -1: m = %d, o = %d, e = %d", h->m, h->o, h->e);
 	if (nq == 0) return AT_OK;
-	if (!q_blob || !q_off || !q_len || !out_target || !out_score || !out_end_i || !out_end_j || !out_state || !out_nhits ||
-	    (rev && !out_strand) || (nt > 0 && (!t_blob || !t_off || !t_len)))
-		return fail(h, AT_ERR_ARG, "at_scan_local: NULL argument");
+	if ((rc = check_list_pointers(h, who, qt, out, rev))) return rc;
 	int32_t maxq = 0;
 	for (int64_t q = 0; q < nq; ++q) {
-		if (q_len[q] < 0 || q_off[q] < 0) return fail(h, AT_ERR_ARG, "query %lld: negative length or offset", (long long)q);
-		if (q_len[q] < 1) return fail(h, AT_ERR_DOMAIN, "query %lld: empty", (long long)q);
+		if ((rc = check_read(h, "query", q, q_len[q], q_off[q], true))) return rc;
 		if (at::localscan_query_ok(q_len[q], h->m, h->u) != AT_OK)
 			return fail(h, AT_ERR_DOMAIN, "at_scan_local: query %lld has %d bases: at most %d, and max(m, u) * length < 2^%d", (long long)q, q_len[q],
 			            at::kLocalScanMaxQuery, at::kLocalScanScoreBits);
 		maxq = std::max(maxq, q_len[q]);
 	}
-	for (int64_t t = 0; t < nt; ++t) {
-		if (t_len[t] < 0 || t_off[t] < 0) return fail(h, AT_ERR_ARG, "target %lld: negative length or offset", (long long)t);
-		if (t_len[t] < 1) return fail(h, AT_ERR_DOMAIN, "target %lld: empty", (long long)t);
-	}
+	for (int64_t t = 0; t < nt; ++t) if ((rc = check_read(h, "target", t, t_len[t], t_off[t], true))) return rc;
 	const int32_t tile = tile_cols > 0 ? tile_cols : at::kLocalScanDefaultTile;
-	return guarded(h, "at_scan_local", [&]() -> int {
-		for (int64_t e = 0; e < nq * k; ++e) { out_target[e] = -1; out_score[e] = 0; out_end_i[e] = 0; out_end_j[e] = 0; out_state[e] = 0; }
-		if (out_strand) for (int64_t e = 0; e < nq * k; ++e) out_strand[e] = -1;
-		for (int64_t q = 0; q < nq; ++q) out_nhits[q] = 0;
-		if (cg) {
-			for (int64_t e = 0; e < nq * k; ++e) { out_ncigar[e] = 0; for (int x = 0; x < 8; ++x) out_stats[e * 8 + x] = -1; }
-			for (int64_t e = 0; e <= nq * k; ++e) out_cigar_off[e] = 0;
-		}
+	return guarded(h, who, [&]() -> int {
+		list_out_init(out, nq, k, co);
 		if (nt == 0) {
 			snprintf(h->cfg, sizeof h->cfg, "local-scan: tile=%d overlap<=0 tiles=0 k=%d strands=%s, 0 blocks, 0 slices; ", tile, k, scan_strands_text(strands));
 			return (int)AT_OK;
 		}
-		int64_t bytes = 0;
-		for (int64_t q = 0; q < nq; ++q) bytes += q_len[q];
-		for (int64_t t = 0; t < nt; ++t) bytes += t_len[t];
-		std::vector<uint8_t> blob((size_t)bytes + 32);
-		std::vector<int64_t> off((size_t)(nq + nt));
-		std::vector<int32_t> len((size_t)(nq + nt));
-		int64_t at = 0;
-		for (int64_t r = 0; r < nq + nt; ++r) {
-			const bool isq = r < nq;
-			const int32_t l = isq ? q_len[r] : t_len[r - nq];
-			if (l) memcpy(blob.data() + at, isq ? q_blob + q_off[r] : t_blob + t_off[r - nq], (size_t)l);
-			off[(size_t)r] = at; len[(size_t)r] = l; at += l;
-		}
 		ReadSet rs;
-		int rc = upload_reads(h, AT_MODE_LOCAL, nq + nt, blob.data(), off.data(), len.data(), &rs, rev ? nq : 0);
-		if (rc) return rc;
-		size_t bkey = 0, bl4 = 0;
-		rc = localscan_lists(h, nq, q_len, nt, t_len, rs, k, use_cutoff, cutoff, strands, tile, out_target, out_score, out_end_i, out_end_j, out_state,
-		                     out_strand, out_nhits, &bkey, &bl4);
-		if (rc || !cg) return rc;
-		return localscan_cigars(h, nq, k, strands, rs, nt, maxq, bkey, bl4, out_target, out_score, out_end_i, out_end_j, flags, out_stats, out_ncigar,
-		                        out_cigar_off, out_cigar, cigar_cap);
+		int rc2 = upload_sets(h, AT_MODE_LOCAL, qt, rev, &rs);
+		if (rc2) return rc2;
+		ListBufs lb;
+		if ((rc2 = localscan_lists(h, qt, rs, k, use_cutoff, cutoff, strands, tile, out, lb)) || !co.any()) return rc2;
+		return localscan_cigars(h, nq, k, strands, rs, nt, maxq, lb, out_target, out_score, out_end_i, out_end_j, flags, co);
 	});
 }
 
@@ -3206,78 +3124,45 @@ struct ScanHitsRun {
 /* the hits of at_scan_hits in their final order and the hits of each query: the blocks and slices of scan_lists; per slice the groups
  * of its pairs are swept by at_scan<W, true> (once more into a buffer of the counted size if the candidates did not fit), the
  * candidates sorted, marked and compacted on the device (at_scanhits.hip.h) and the kept ones fetched */
-static int scan_hits_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64_t nt, const int32_t *t_len, const ReadSet &rs,
-                           int32_t max_dist, int32_t min_sep, int strands, int32_t tile, int64_t cand_cap,
-                           std::vector<at::ScanHit> &hits, std::vector<int32_t> &qcount, ScanHitsRun &run)
+static int scan_hits_lists(at_handle *h, const QuerySets &qt, const ReadSet &rs, int32_t max_dist, int32_t min_sep, int strands, int32_t tile,
+                           int64_t cand_cap, std::vector<at::ScanHit> &hits, std::vector<int32_t> &qcount, ScanHitsRun &run)
 {
-	const int enc = strands != AT_STRAND_FWD, two = strands == AT_STRAND_BOTH;
-	const int64_t nv = nq << two;
-	std::vector<int> qs((size_t)nq), qperm((size_t)nv);
-	for (int64_t q = 0; q < nq; ++q) qs[(size_t)q] = (int)q;
-	std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return q_len[a] < q_len[b]; });
-	for (int64_t q = 0; q < nq; ++q) {
-		const int c = qs[(size_t)q];
-		if (two) { qperm[(size_t)(2 * q)] = c << 1; qperm[(size_t)(2 * q + 1)] = (c << 1) | 1; }
-		else qperm[(size_t)q] = enc ? (c << 1) | 1 : c;
+	const int64_t nq = qt.nq, nt = qt.nt;
+	const at::QueryOrder qo = at::query_order(nq, qt.q_len, strands);
+	ScanSweep sw(qt, qo.enc, tile, rs);
+	int64_t tsum = 0, most = 0;
+	for (int64_t t = 0; t < nt; ++t) tsum += qt.t_len[t];
+	std::vector<at::QueryBlock> blocks;
+	for (const at::QueryBlock &B : qo.blocks) {
+		if (B.l1 < 1) continue;                                   /* a query of length 0 has no hits */
+		blocks.push_back(B);
+		most = std::max<int64_t>(most, (int64_t)B.nqb * nt);
 	}
-	std::vector<long long> gpre((size_t)nt + 1);
-	gpre[0] = 0;
-	int64_t tsum = 0;
-	for (int64_t t = 0; t < nt; ++t) {
-		gpre[(size_t)t + 1] = gpre[(size_t)t] + at::scan_groups(t_len[t], tile);
-		tsum += t_len[t];
-	}
-	const long long gall = gpre[(size_t)nt];
-	struct Block { int qa, nqb; int32_t l1; };
-	std::vector<Block> blocks;
-	int64_t most = 0;
-	for (int64_t a = 0, b; a < nq; a = b) {
-		const int32_t L = q_len[qs[(size_t)a]];
-		for (b = a; b < nq && q_len[qs[(size_t)b]] == L; ++b) {}
-		if (L < 1) continue;                                   /* a query of length 0 has no hits */
-		blocks.push_back({(int)(a << two), (int)((b - a) << two), L});
-		most = std::max<int64_t>(most, ((b - a) << two) * nt);
-	}
-	int64_t chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
-	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(std::max<int64_t>(most, 1), 1LL << 28)));
-	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t bq = al((size_t)nv * 4), bg = al(((size_t)nt + 1) * 8), bc = al((size_t)nq * 4);
-	int rc = grow(h, &h->d_desc, &h->desc_bytes, 256 + bg + bq + bc);
+	const int64_t chunk = at::slice_clamp(env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault), most);
+	unsigned long long *d_ncand = nullptr; long long *d_gpre = nullptr; int *d_qperm = nullptr, *d_qcount = nullptr;
+	int rc = carve(h, &h->d_desc, &h->desc_bytes, [&](Carver &c) {
+		d_ncand = c.take<unsigned long long>(1); d_gpre = c.take<long long>((size_t)nt + 1);
+		d_qperm = c.take<int>((size_t)qo.nv); d_qcount = c.take<int>((size_t)nq);
+	});
 	if (rc) return rc;
-	char *dd = (char *)h->d_desc;
-	unsigned long long *d_ncand = (unsigned long long *)dd;
-	long long *d_gpre = (long long *)(dd + 256);
-	int *d_qperm = (int *)(dd + 256 + bg), *d_qcount = (int *)(dd + 256 + bg + bq);
 	hipStream_t s = h->stream;
-	HIP_TRY(h, hipMemcpyAsync(d_qperm, qperm.data(), (size_t)nv * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemcpyAsync(d_gpre, gpre.data(), ((size_t)nt + 1) * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_qperm, qo.qperm.data(), (size_t)qo.nv * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemcpyAsync(d_gpre, sw.gpre.data(), ((size_t)nt + 1) * 8, hipMemcpyHostToDevice, s));
 	HIP_TRY(h, hipMemsetAsync(d_qcount, 0, (size_t)nq * 4, s));
-	/* the candidate block of a capacity: keys and values before and behind the sort, flags, prefix sums, hit records */
-	struct Cand { unsigned long long *k0, *k1; long long *off; int *v0, *v1, *flag; at::ScanHit *hit; };
-	auto cand_bytes = [&](int64_t cap) { return 2 * al((size_t)cap * 8) + al(((size_t)cap + 1) * 8) + 3 * al((size_t)cap * 4) + al((size_t)cap * sizeof(at::ScanHit)); };
-	auto cand_at = [&](int64_t cap) {
-		char *p = (char *)h->d_cand;
-		Cand c;
-		c.k0 = (unsigned long long *)p; p += al((size_t)cap * 8);
-		c.k1 = (unsigned long long *)p; p += al((size_t)cap * 8);
-		c.off = (long long *)p; p += al(((size_t)cap + 1) * 8);
-		c.v0 = (int *)p; p += al((size_t)cap * 4);
-		c.v1 = (int *)p; p += al((size_t)cap * 4);
-		c.flag = (int *)p; p += al((size_t)cap * 4);
-		c.hit = (at::ScanHit *)p;
-		return c;
+	/* the candidate block of a capacity: keys and values before and behind the sort, prefix sums, flags, hit records */
+	struct Cand { unsigned long long *k0, *k1; long long *off; int *v0, *v1, *flag; at::ScanHit *hit; } cd = {};
+	auto cand_carve = [&](int64_t cap) {
+		return carve(h, &h->d_cand, &h->cand_bytes, [&](Carver &c) {
+			cd.k0 = c.take<unsigned long long>((size_t)cap); cd.k1 = c.take<unsigned long long>((size_t)cap); cd.off = c.take<long long>((size_t)cap + 1);
+			cd.v0 = c.take<int>((size_t)cap); cd.v1 = c.take<int>((size_t)cap); cd.flag = c.take<int>((size_t)cap); cd.hit = c.take<at::ScanHit>((size_t)cap);
+		});
 	};
-	struct Ev { hipEvent_t e[3] = {nullptr, nullptr, nullptr}; ~Ev() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
-	for (hipEvent_t &x : ev.e) HIP_TRY(h, hipEventCreate(&x));
-	auto items_before = [&](int64_t x) { return (long long)(x / nt) * gall + gpre[(size_t)(x % nt)]; };
-	run.gall = gall; run.nblocks = (long long)blocks.size();
-	for (const Block &B : blocks) {
+	StreamEvents ev;
+	if ((rc = ev.create(h, 3))) return rc;
+	run.gall = sw.gall; run.nblocks = (long long)blocks.size();
+	for (const at::QueryBlock &B : blocks) {
 		const int64_t bp = (int64_t)B.nqb * nt;
-		const int w = at::class_rows(at::kMyersLaneWords, B.l1);
-		const void *fn = at_scan_hits_kernel(w);
-		if (!fn) return fail(h, AT_ERR_ARG, "no scan kernel for %d words per lane", w);
-		int occ = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64, 0) != hipSuccess || occ <= 0) occ = 8;
+		if ((rc = sw.block(h, B.l1, at_scan_hits_kernel))) return rc;
 		const int32_t c = at::scan_hits_bound(B.l1, max_dist);
 		run.ov_most = std::max(run.ov_most, (int)at::scan_overlap(B.l1, 1, c));
 		for (int64_t s0 = 0; s0 < bp; s0 += chunk) {
@@ -3286,25 +3171,17 @@ static int scan_hits_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64
 			const long double mc = ((long double)(n / nt) + 2.0L) * (long double)tsum;   /* (the slice touches at most n / nt + 2 entries) */
 			const int64_t most_cand = mc > 4e18L ? (int64_t)4e18L : std::max<int64_t>(1, (int64_t)mc);
 			int64_t cap = std::min<int64_t>(cand_cap > 0 ? cand_cap : at::kScanHitsDefaultCand, most_cand);
-			at::ScanArgs sa;
-			memset(&sa, 0, sizeof sa);
-			sa.y0 = items_before(s0); sa.nitems = items_before(s0 + n) - sa.y0;
-			sa.s0 = s0; sa.npairs = n; sa.ntb = nt; sa.gall = gall; sa.gpre = d_gpre;
-			sa.qa = B.qa; sa.nq = (int)nq; sa.enc = enc; sa.nrev0 = (int)(nq + nt); sa.qperm = d_qperm;
-			sa.seq = rs.d_words; sa.swoff = (const long long *)rs.d_swoff; sa.slen = rs.d_len;
-			sa.tile = tile; sa.use_cutoff = 1; sa.cutoff = c;
-			const long long grid = std::max(1LL, std::min<long long>(sa.nitems, (long long)occ * h->ncu));
+			at::ScanArgs sa = sw.slice(B.qa, s0, n, d_gpre, d_qperm, 1, c);
+			const long long grid = sw.grid(h, sa);
 			unsigned long long ncand = 0;
 			for (int turn = 0;; ++turn) {
-				rc = grow(h, &h->d_cand, &h->cand_bytes, cand_bytes(cap));
-				if (rc) return rc;
-				const Cand cd = cand_at(cap);
+				if ((rc = cand_carve(cap))) return rc;
 				sa.cand_n = d_ncand; sa.cand_cap = cap; sa.cand_key = cd.k0; sa.cand_val = cd.v0;
 				HIP_TRY(h, hipMemsetAsync(d_ncand, 0, 8, s));
 				if (int rcq = ensure_queue(h, s)) return rcq;
 				sa.queue = h->d_queue;
 				HIP_TRY(h, hipEventRecord(ev.e[0], s));
-				HIP_TRY(h, at_scan_hits_launch(&sa, w, (unsigned)grid, s));
+				HIP_TRY(h, at_scan_hits_launch(&sa, sw.w, (unsigned)grid, s));
 				HIP_TRY(h, hipEventRecord(ev.e[1], s));
 				HIP_TRY(h, hipMemcpyAsync(&ncand, d_ncand, 8, hipMemcpyDeviceToHost, s));
 				HIP_TRY(h, hipStreamSynchronize(s));
@@ -3320,15 +3197,10 @@ static int scan_hits_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64
 				cap = (int64_t)ncand;
 				++run.resweeps;
 			}
-			if (run.nslices == 0) {
-				char buf[200];
-				snprintf(buf, sizeof buf, "myers-scan-hits bits=2 words/lane=%d (1 read/wave, 64 tiles) lds=0B waves/cu<=%d grid=%lld", w, occ, grid);
-				run.cfg0 = buf;
-			}
+			if (run.nslices == 0) run.cfg0 = sw.text("myers-scan-hits", grid);
 			++run.nslices;
 			run.cand += (long long)ncand;
 			if (ncand == 0) continue;
-			const Cand cd = cand_at(cap);
 			const long long nc = (long long)ncand;
 			size_t tmp_bytes = 0;
 			HIP_TRY(h, at_scanhits_sort(nullptr, &tmp_bytes, cd.k0, cd.k1, cd.v0, cd.v1, nc, n, s));
@@ -3337,7 +3209,7 @@ static int scan_hits_lists(at_handle *h, int64_t nq, const int32_t *q_len, int64
 			HIP_TRY(h, at_scanhits_sort(h->d_sorttmp, &tmp_bytes, cd.k0, cd.k1, cd.v0, cd.v1, nc, n, s));
 			at::ScanHitsArgs ha;
 			memset(&ha, 0, sizeof ha);
-			ha.n = nc; ha.key = cd.k1; ha.val = cd.v1; ha.s0 = s0; ha.ntb = nt; ha.qa = B.qa; ha.enc = enc; ha.nrev0 = (int)(nq + nt);
+			ha.n = nc; ha.key = cd.k1; ha.val = cd.v1; ha.s0 = s0; ha.ntb = nt; ha.qa = B.qa; ha.enc = qo.enc; ha.nrev0 = (int)(nq + nt);
 			ha.min_sep = min_sep; ha.qperm = d_qperm; ha.slen = rs.d_len; ha.flag = cd.flag; ha.off = cd.off; ha.hits = cd.hit; ha.qcount = d_qcount;
 			HIP_TRY(h, at_scanhits_mark_launch(&ha, h->ncu, s));
 			rc = scan_nops_device(h, nc, cd.flag, (int64_t *)cd.off, s);
@@ -3377,39 +3249,30 @@ extern "C" int at_scan_hits(at_handle *h,
                             int32_t *out_target, int32_t *out_score, int32_t *out_end_j, int32_t *out_strand,
                             int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off, uint32_t *out_cigar, int64_t cigar_cap)
 {
+	const char *who = "at_scan_hits";
 	if (!h) return fail(nullptr, AT_ERR_ARG, "at_scan_hits: NULL handle");
-	if (nq < 0 || nt < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "at_scan_hits: negative size");
+	const QuerySets qt = {nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len};
+	const CigarOut co = {out_stats, out_ncigar, out_cigar_off, out_cigar, cigar_cap};
+	int rc = check_sizes(h, who, nq, nt, cigar_cap);
+	if (rc) return rc;
 	if (max_dist < 0) return fail(h, AT_ERR_ARG, "at_scan_hits: max_dist = %d is negative", max_dist);
 	if (min_sep < AT_SCAN_SEP_READ) return fail(h, AT_ERR_ARG, "at_scan_hits: min_sep = %d (a distance in columns, 0, or AT_SCAN_SEP_READ)", min_sep);
 	if (cand_cap < 0 || hit_cap < 0) return fail(h, AT_ERR_ARG, "at_scan_hits: negative capacity");
-	if (strands < AT_STRAND_FWD || strands > AT_STRAND_BOTH) return fail(h, AT_ERR_ARG, "at_scan_hits: strands = %d outside 1..3", strands);
-	if (tile_cols < 0 || (tile_cols & 15))
-		return fail(h, AT_ERR_ARG, "at_scan_hits: tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)", tile_cols, at::kScanDefaultTile);
-	if (flags & ~AT_CIGAR_M) return fail(h, AT_ERR_ARG, "at_scan_hits: flags = %d (AT_CIGAR_M or 0)", flags);
-	const bool rev = strands != AT_STRAND_FWD;
-	const bool cg = out_stats || out_ncigar || out_cigar_off || out_cigar;
-	if (cg && (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)))
-		return fail(h, AT_ERR_ARG, "at_scan_hits: the CIGAR outputs are either all NULL or all given");
-	if (nq + nt >= (1LL << 31)) return fail(h, AT_ERR_ARG, "at_scan_hits: %lld queries + %lld targets: at most 2^31 - 1 reads", (long long)nq, (long long)nt);
-	if (rev && (nt >= (1LL << 30) || 2 * nq + nt >= (1LL << 31)))
-		return fail(h, AT_ERR_ARG, "at_scan_hits: %lld queries, %lld targets: a reverse strand needs nt < 2^30 and 2 nq + nt < 2^31", (long long)nq, (long long)nt);
-	if (h->comm) return fail(h, AT_ERR_DOMAIN, "at_scan_hits: one GPU only (this handle belongs to a multi-process job)");
+	if ((rc = check_options(h, who, strands, tile_cols, at::kScanDefaultTile, flags, co, nq, nt)) || (rc = check_one_gpu(h, who))) return rc;
+	const bool rev = strands != AT_STRAND_FWD, cg = co.any();
 	if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "at_scan_hits needs the unit mismatch cost: u = %d, not 1", h->u);
-	if (!out_hit_off) return fail(h, AT_ERR_ARG, "at_scan_hits: NULL argument");
-	if (nq > 0 && (!q_blob || !q_off || !q_len || (nt > 0 && (!t_blob || !t_off || !t_len))))
-		return fail(h, AT_ERR_ARG, "at_scan_hits: NULL argument");
-	if (hit_cap > 0 && (!out_target || !out_score || !out_end_j || (rev && !out_strand)))
+	if (!out_hit_off || (nq > 0 && (!q_blob || !q_off || !q_len || (nt > 0 && (!t_blob || !t_off || !t_len)))) ||
+	    (hit_cap > 0 && (!out_target || !out_score || !out_end_j || (rev && !out_strand))))
 		return fail(h, AT_ERR_ARG, "at_scan_hits: NULL argument");
 	int32_t maxq = 0;
 	for (int64_t q = 0; q < nq; ++q) {
-		if (q_len[q] < 0 || q_off[q] < 0) return fail(h, AT_ERR_ARG, "query %lld: negative length or offset", (long long)q);
+		if ((rc = check_read(h, "query", q, q_len[q], q_off[q], false))) return rc;
 		if (q_len[q] > at::kScanMaxQuery) return fail(h, AT_ERR_DOMAIN, "at_scan_hits: query %lld has %d bases, more than %d", (long long)q, q_len[q], at::kScanMaxQuery);
 		maxq = std::max(maxq, q_len[q]);
 	}
-	for (int64_t t = 0; t < nt; ++t)
-		if (t_len[t] < 0 || t_off[t] < 0) return fail(h, AT_ERR_ARG, "target %lld: negative length or offset", (long long)t);
+	for (int64_t t = 0; t < nt; ++t) if ((rc = check_read(h, "target", t, t_len[t], t_off[t], false))) return rc;
 	const int32_t tile = tile_cols > 0 ? tile_cols : at::kScanDefaultTile;
-	return guarded(h, "at_scan_hits", [&]() -> int {
+	return guarded(h, who, [&]() -> int {
 		for (int64_t q = 0; q <= nq; ++q) out_hit_off[q] = 0;
 		ScanHitsRun run;
 		auto config = [&]() {
@@ -3422,26 +3285,13 @@ extern "C" int at_scan_hits(at_handle *h,
 			config();
 			return (int)AT_OK;
 		}
-		int64_t bytes = 0;
-		for (int64_t q = 0; q < nq; ++q) bytes += q_len[q];
-		for (int64_t t = 0; t < nt; ++t) bytes += t_len[t];
-		std::vector<uint8_t> blob((size_t)bytes + 32);
-		std::vector<int64_t> off((size_t)(nq + nt));
-		std::vector<int32_t> len((size_t)(nq + nt));
-		int64_t at = 0;
-		for (int64_t r = 0; r < nq + nt; ++r) {
-			const bool isq = r < nq;
-			const int32_t l = isq ? q_len[r] : t_len[r - nq];
-			if (l) memcpy(blob.data() + at, isq ? q_blob + q_off[r] : t_blob + t_off[r - nq], (size_t)l);
-			off[(size_t)r] = at; len[(size_t)r] = l; at += l;
-		}
 		ReadSet rs;
-		int rc = upload_reads(h, AT_MODE_EDIT, nq + nt, blob.data(), off.data(), len.data(), &rs, rev ? nq : 0);
+		int rc = upload_sets(h, AT_MODE_EDIT, qt, rev, &rs);
 		if (rc) return rc;
 		if (rs.bits != 2) return fail(h, AT_ERR_DOMAIN, "at_scan_hits needs 2-bit reads: some base of a query or a target is not one of ACGT");
 		std::vector<at::ScanHit> hits;
 		std::vector<int32_t> qcount;
-		rc = scan_hits_lists(h, nq, q_len, nt, t_len, rs, max_dist, min_sep, strands, tile, cand_cap, hits, qcount, run);
+		rc = scan_hits_lists(h, qt, rs, max_dist, min_sep, strands, tile, cand_cap, hits, qcount, run);
 		if (rc) return rc;
 		config();
 		const int64_t nh = (int64_t)hits.size();
@@ -3456,44 +3306,33 @@ extern "C" int at_scan_hits(at_handle *h,
 		if (!cg) return (int)AT_OK;
 		out_cigar_off[0] = 0;
 		if (nh == 0) return (int)AT_OK;
-		/* the window pass over the hits, in pieces that keep its descriptor and op buffers moderate */
-		const int64_t piece_hits = 1LL << 20, piece_ops = 1LL << 30;
-		auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+		/* the window pass over the hits, in pieces that keep its descriptor and op buffers moderate: each piece as lists of its own
+		 * (key, query, end column of every hit) */
 		std::vector<unsigned long long> lkey;
-		std::vector<int32_t> lej, leq, lei, p_ncigar, p_stats;
+		std::vector<int32_t> lej, leq, lei;
 		std::vector<int64_t> p_off;
 		std::string wcfg;
 		for (int64_t a = 0, b; a < nh; a = b) {
-			int64_t ops = 0;
-			for (b = a; b < nh && b - a < piece_hits; ++b) {
-				const at::ScanHit &x = hits[(size_t)b];
-				const int64_t one = 2LL * q_len[x.query] + x.score + 16;
-				if (b > a && ops + one > piece_ops) break;
-				ops += one;
-			}
+			b = at::piece_end(a, nh, 1LL << 20, 1LL << 30, [&](int64_t e) { return 2LL * q_len[hits[(size_t)e].query] + hits[(size_t)e].score + 16; });
 			const int64_t n = b - a;
 			lkey.assign((size_t)n, 0); lej.assign((size_t)n, 0); leq.assign((size_t)n, 0); lei.assign((size_t)n, 0);
 			for (int64_t e = 0; e < n; ++e) {
 				const at::ScanHit &x = hits[(size_t)(a + e)];
-				const uint32_t low = ~(uint32_t)(rev ? ((uint32_t)x.target << 1) | (uint32_t)x.strand : (uint32_t)x.target);
-				lkey[(size_t)e] = ((unsigned long long)((uint32_t)(-x.score) ^ 0x80000000u) << 32) | low;
+				lkey[(size_t)e] = at::list_key(-x.score, x.target, x.strand, rev);
 				lej[(size_t)e] = x.end_j; leq[(size_t)e] = x.query; lei[(size_t)e] = q_len[x.query];
 			}
-			const size_t bkey = al((size_t)n * 8), bl4 = al((size_t)n * 4);
-			rc = grow(h, &h->d_str, &h->str_bytes, bkey + 3 * bl4);
-			if (rc) return rc;
-			char *dl = (char *)h->d_str;
+			ListBufs lb;
+			if ((rc = list_bufs(h, (size_t)n, false, &lb))) return rc;
 			hipStream_t s = h->stream;
-			HIP_TRY(h, hipMemcpyAsync(dl, lkey.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-			HIP_TRY(h, hipMemcpyAsync(dl + bkey, leq.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-			HIP_TRY(h, hipMemcpyAsync(dl + bkey + bl4, lej.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(h, hipMemcpyAsync(lb.key, lkey.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+			HIP_TRY(h, hipMemcpyAsync(lb.ei, leq.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(h, hipMemcpyAsync(lb.ej, lej.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
 			HIP_TRY(h, hipStreamSynchronize(s));
 			const int64_t base = out_cigar_off[a];
-			const int64_t room = std::max<int64_t>(0, cigar_cap - base);
 			p_off.assign((size_t)n + 1, 0);
-			rc = scan_cigars(h, nq, 1, strands, rs, nt, maxq, bkey, bl4, out_target + a, out_score + a, lei.data(), out_end_j + a, flags,
-			                 out_stats + a * 8, out_ncigar + a, p_off.data(), room > 0 ? out_cigar + base : nullptr, room, n,
-			                 (const int *)(dl + bkey), "at_scan_hits");
+			const int64_t room = std::max<int64_t>(0, cigar_cap - base);
+			const CigarOut piece = {out_stats + a * 8, out_ncigar + a, p_off.data(), room > 0 ? out_cigar + base : nullptr, room};
+			rc = scan_cigars(h, nq, 1, strands, rs, nt, maxq, lb, out_target + a, out_score + a, lei.data(), out_end_j + a, flags, piece, n, who);
 			if (rc) return rc;
 			for (int64_t e = 1; e <= n; ++e) out_cigar_off[a + e] = base + p_off[(size_t)e];
 			if (wcfg.empty()) { const char *w = strstr(h->cfg, "; windows: "); wcfg = w ? w : ""; }
@@ -3638,14 +3477,15 @@ struct PairHitsRun { int64_t nslices = 0, chunk = 0; std::string cfg0; };
 static int allpairs_hit_slices(at_handle *h, int mode, int64_t nreads, const ReadSet &rs, int64_t first_pair, int64_t npairs,
                                int64_t chunk, int32_t threshold, std::vector<at::PairHit> &hits, PairHitsRun &run)
 {
-	if (chunk <= 0) chunk = env_ll("AT_ALLPAIRS_CHUNK", 4LL << 20);
-	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(npairs, 1LL << 28)));
-	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t b_res = al((size_t)chunk * 4), b_off = al((size_t)(chunk + 1) * 8), b_rec = al((size_t)chunk * sizeof(at::PairHit));
-	int rc = grow(h, &h->d_out, &h->out_bytes, 2 * 4 * b_res);
-	if (rc) return rc;
+	if (chunk <= 0) chunk = env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault);
+	chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, std::min<int64_t>(npairs, at::kSliceMost)));
+	int32_t *d_res[2][4]; int *d_flag = nullptr; long long *d_off = nullptr; unsigned long long *d_slots[2]; at::PairHit *d_rec[2];
+	int rc = carve(h, &h->d_out, &h->out_bytes, [&](Carver &c) { for (auto &set : d_res) for (int32_t *&x : set) x = c.take<int32_t>((size_t)chunk); });
 	/* [flags | prefix sums | 2 x (the two 64-bit slots | the slice's records)] */
-	rc = grow(h, &h->d_cand, &h->cand_bytes, b_res + b_off + 2 * (256 + b_rec));
+	if (!rc) rc = carve(h, &h->d_cand, &h->cand_bytes, [&](Carver &c) {
+		d_flag = c.take<int>((size_t)chunk); d_off = c.take<long long>((size_t)chunk + 1);
+		for (int q = 0; q < 2; ++q) { d_slots[q] = c.take<unsigned long long>(1); d_rec[q] = c.take<at::PairHit>((size_t)chunk); }
+	});
 	if (rc) return rc;
 	if (h->pin_bytes < 256) {
 		if (h->h_pin) { (void)hipHostFree(h->h_pin); h->h_pin = nullptr; h->pin_bytes = 0; }
@@ -3663,12 +3503,6 @@ static int allpairs_hit_slices(at_handle *h, int mode, int64_t nreads, const Rea
 	}
 	hipStream_t s = h->stream, cs = h->copy_stream;
 	const int64_t nchunks = (npairs + chunk - 1) / chunk;
-	char *dsel = (char *)h->d_cand;
-	int *d_flag = (int *)dsel;
-	long long *d_off = (long long *)(dsel + b_res);
-	auto dres = [&](int q, int a) { return (int32_t *)((char *)h->d_out + ((size_t)q * 4 + (size_t)a) * b_res); };
-	auto dslots = [&](int q) { return (unsigned long long *)(dsel + b_res + b_off + (size_t)q * (256 + b_rec)); };
-	auto drec = [&](int q) { return (at::PairHit *)(dsel + b_res + b_off + (size_t)q * (256 + b_rec) + 256); };
 	auto hslots = [&](int q) { return (volatile unsigned long long *)((char *)h->h_pin + (size_t)q * 64); };
 	auto deliver = [&](int64_t c) -> int {
 		const int q = (int)(c & 1);
@@ -3681,7 +3515,7 @@ static int allpairs_hit_slices(at_handle *h, int mode, int64_t nreads, const Rea
 		if (kept > 0) {
 			const size_t was = hits.size();
 			hits.resize(was + (size_t)kept);
-			HIP_TRY(h, hipMemcpyAsync(hits.data() + was, drec(q), (size_t)kept * sizeof(at::PairHit), hipMemcpyDeviceToHost, cs));
+			HIP_TRY(h, hipMemcpyAsync(hits.data() + was, d_rec[q], (size_t)kept * sizeof(at::PairHit), hipMemcpyDeviceToHost, cs));
 			HIP_TRY(h, hipStreamSynchronize(cs));
 		}
 		return AT_OK;
@@ -3691,17 +3525,17 @@ static int allpairs_hit_slices(at_handle *h, int mode, int64_t nreads, const Rea
 		const int64_t lo = c * chunk, n = std::min(chunk, npairs - lo);
 		/* (slice c - 2, the last user of buffer set q, was delivered before slice c - 1 was queued) */
 		rc = align_device(h, mode, n, rs.d_words, rs.bits, rs.d_swoff, rs.d_len, rs.d_swoff, rs.d_len, rs.maxlen, rs.maxlen, 0, 0,
-		                  dres(q, 0), dres(q, 1), dres(q, 2), dres(q, 3), nullptr, nullptr, nullptr, s, nreads, first_pair + lo);
+		                  d_res[q][0], d_res[q][1], d_res[q][2], d_res[q][3], nullptr, nullptr, nullptr, s, nreads, first_pair + lo);
 		if (rc) { (void)hipDeviceSynchronize(); return rc; }
 		if (c == 0) run.cfg0 = h->cfg;
 		at::PairHitsArgs pa;
 		memset(&pa, 0, sizeof pa);
 		pa.n = n; pa.first = first_pair + lo; pa.nreads = nreads;
-		pa.score = dres(q, 0); pa.end_i = dres(q, 1); pa.end_j = dres(q, 2); pa.state = dres(q, 3);
+		pa.score = d_res[q][0]; pa.end_i = d_res[q][1]; pa.end_j = d_res[q][2]; pa.state = d_res[q][3];
 		pa.threshold = threshold; pa.is_edit = mode == AT_MODE_EDIT ? 1 : 0;
-		pa.flag = d_flag; pa.off = d_off; pa.hits = drec(q); pa.cap = chunk; pa.slots = dslots(q);
+		pa.flag = d_flag; pa.off = d_off; pa.hits = d_rec[q]; pa.cap = chunk; pa.slots = d_slots[q];
 		auto select = [&]() -> int {
-			HIP_TRY(h, hipMemsetAsync(dslots(q), 0xff, 8, s));
+			HIP_TRY(h, hipMemsetAsync(d_slots[q], 0xff, 8, s));
 			HIP_TRY(h, at_pairhits_flag_launch(&pa, h->ncu, s));
 			if (int rcs = scan_nops_device(h, n, d_flag, (int64_t *)d_off, s)) return rcs;
 			HIP_TRY(h, at_pairhits_emit_launch(&pa, h->ncu, s));
@@ -3712,7 +3546,7 @@ static int allpairs_hit_slices(at_handle *h, int mode, int64_t nreads, const Rea
 		if (rc == AT_OK && c >= 1) rc = deliver(c - 1);
 		if (rc) { (void)hipDeviceSynchronize(); return rc; }
 		HIP_TRY(h, hipStreamWaitEvent(cs, h->ev_sweep[q], 0));
-		HIP_TRY(h, hipMemcpyAsync((void *)hslots(q), dslots(q), 16, hipMemcpyDeviceToHost, cs));
+		HIP_TRY(h, hipMemcpyAsync((void *)hslots(q), d_slots[q], 16, hipMemcpyDeviceToHost, cs));
 		HIP_TRY(h, hipEventRecord(h->ev_copy[q], cs));
 	}
 	rc = deliver(nchunks - 1);
@@ -3723,64 +3557,34 @@ static int allpairs_hit_slices(at_handle *h, int mode, int64_t nreads, const Rea
 
 /* the alignments of n hits (one piece): pair list and op slots from the records, the sweep with tracebacks, the runs, the check */
 static int pairhits_cigars(at_handle *h, int mode, const ReadSet &rs, const at::PairHit *hits, int64_t n, int64_t ops_bytes, int flags,
-                           int32_t *out_stats, int32_t *out_ncigar, int64_t *p_off, uint32_t *out_cigar, int64_t room, std::string *tbcfg)
+                           const CigarOut &co, std::string *tbcfg)
 {
-	auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-	const size_t b8 = al((size_t)(n + 1) * 8), b4 = al((size_t)n * 4), bst = al((size_t)n * 32), brec = al((size_t)n * sizeof(at::PairHit));
-	const int64_t dcap = std::min<int64_t>(room, ops_bytes);   /* (a list has no more runs than ops) */
-	int rc = grow(h, &h->d_out, &h->out_bytes, brec + 3 * b8 + 8 * b4);
-	if (rc) return rc;
-	rc = grow(h, &h->d_str, &h->str_bytes, al((size_t)ops_bytes + 64));
-	if (rc) return rc;
-	rc = grow(h, &h->d_cg, &h->cg_bytes, b4 + bst + b8 + al((size_t)dcap * 4) + 256);
-	if (rc) return rc;
-	char *dw = (char *)h->d_out, *dc = (char *)h->d_cg;
-	at::PairHit *d_rec = (at::PairHit *)dw;
-	int64_t *d_woff1 = (int64_t *)(dw + brec), *d_woff2 = (int64_t *)(dw + brec + b8), *d_ops_off = (int64_t *)(dw + brec + 2 * b8);
-	int32_t *d4[8];
-	for (int x = 0; x < 8; ++x) d4[x] = (int32_t *)(dw + brec + 3 * b8 + (size_t)x * b4);
-	int32_t *d_len1 = d4[0], *d_len2 = d4[1], *d_nslot = d4[2], *d_sc = d4[3], *d_ei = d4[4], *d_ej = d4[5], *d_st = d4[6], *d_nops = d4[7];
-	int32_t *d_ncigar = (int32_t *)dc, *d_stats = (int32_t *)(dc + b4);
-	int64_t *d_coff = (int64_t *)(dc + b4 + bst);
-	uint32_t *d_cigar = (uint32_t *)(dc + b4 + bst + b8);
-	int *d_bad = (int *)(dc + b4 + bst + b8 + al((size_t)dcap * 4));
-	uint8_t *d_ops = (uint8_t *)h->d_str;
+	const int64_t dcap = std::min<int64_t>(co.cap, ops_bytes);   /* (a list has no more runs than ops) */
 	hipStream_t s = h->stream;
-	HIP_TRY(h, hipMemcpyAsync(d_rec, hits, (size_t)n * sizeof(at::PairHit), hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemsetAsync(d_bad, 0, 4, s));
+	WindowBufs w;
+	int rc = window_carve(h, n, dcap, (size_t)n * sizeof(at::PairHit), false, false, &h->d_str, &h->str_bytes, ((size_t)ops_bytes + 64 + 255) & ~(size_t)255, w);
+	if (rc) return rc;
+	HIP_TRY(h, hipMemcpyAsync(w.front, hits, (size_t)n * sizeof(at::PairHit), hipMemcpyHostToDevice, s));
+	HIP_TRY(h, hipMemsetAsync(w.bad, 0, 4, s));
 	at::PairHitsDescArgs da;
 	memset(&da, 0, sizeof da);
-	da.n = n; da.hits = d_rec; da.swoff = (const long long *)rs.d_swoff; da.slen = rs.d_len;
-	da.woff1 = (long long *)d_woff1; da.woff2 = (long long *)d_woff2; da.len1 = d_len1; da.len2 = d_len2; da.nslot = d_nslot;
-	da.score2 = d_sc; da.end_i2 = d_ei; da.end_j2 = d_ej; da.bad = d_bad;
+	da.n = n; da.hits = (const at::PairHit *)w.front; da.swoff = (const long long *)rs.d_swoff; da.slen = rs.d_len;
+	da.woff1 = (long long *)w.woff1; da.woff2 = (long long *)w.woff2; da.len1 = w.len1; da.len2 = w.len2; da.nslot = w.aux;
+	da.score2 = w.sc; da.end_i2 = w.ei; da.end_j2 = w.ej; da.bad = w.bad;
 	HIP_TRY(h, at_pairhits_desc_launch(&da, h->ncu, s));
-	rc = scan_nops_device(h, n, d_nslot, d_ops_off, s);
-	if (rc) { (void)hipStreamSynchronize(s); return rc; }
-	rc = align_device(h, mode, n, rs.d_words, rs.bits, d_woff1, d_len1, d_woff2, d_len2, rs.maxlen, rs.maxlen, 0, 1, d_sc, d_ei, d_ej, d_st,
-	                  d_ops, d_ops_off, d_nops, s, 0, 0);
+	rc = scan_nops_device(h, n, w.aux, w.ops_off, s);
+	if (!rc) rc = align_device(h, mode, n, rs.d_words, rs.bits, w.woff1, w.len1, w.woff2, w.len2, rs.maxlen, rs.maxlen, 0, 1, w.sc, w.ei, w.ej, w.st,
+	                           w.ops, w.ops_off, w.nops, s, 0, 0);
 	if (rc) { (void)hipStreamSynchronize(s); return rc; }
 	if (tbcfg && tbcfg->empty()) *tbcfg = h->cfg;
-	rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, d_woff1, d_woff2, d_ei, d_ej, d_ops, d_ops_off, d_nops, flags, d_ncigar, d_stats, d_coff,
-	                           d_cigar, dcap, s);
+	rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, w.woff1, w.woff2, w.ei, w.ej, w.ops, w.ops_off, w.nops, flags, w.ncigar, w.stats, w.coff, w.cigar, dcap, s);
 	if (rc) { (void)hipStreamSynchronize(s); return rc; }
 	HIP_TRY(h, at_pairhits_check_launch(&da, h->ncu, s));
-	int bad = 0;
-	HIP_TRY(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipMemcpyAsync(out_ncigar, d_ncigar, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipMemcpyAsync(out_stats, d_stats, (size_t)n * 32, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipMemcpyAsync(p_off, d_coff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(h, hipStreamSynchronize(s));
-	if (bad) return fail(h, AT_ERR_RANGE, "at_allpairs_hits: the traceback pass does not reproduce a hit's score and end cell");
+	rc = window_fetch(h, w, n, "at_allpairs_hits: the traceback pass does not reproduce a hit's score and end cell", co.ncigar, co.stats, co.off);
+	if (rc) return rc;
 	for (int64_t e = 0; e < n; ++e)
-		if (out_ncigar[e] < 0) return fail(h, AT_ERR_DOMAIN, "pair %lld: traceback inconsistent with its sequences", hits[e].pair);
-	/* the words of the hits that end within the caller's room: a prefix of the device buffer */
-	int64_t fit = 0;
-	for (int64_t e = 0; e < n; ++e) if (p_off[e + 1] <= room) fit = p_off[e + 1]; else break;
-	if (fit > 0) {
-		HIP_TRY(h, hipMemcpyAsync(out_cigar, d_cigar, (size_t)fit * 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(h, hipStreamSynchronize(s));
-	}
-	return AT_OK;
+		if (co.ncigar[e] < 0) return fail(h, AT_ERR_DOMAIN, "pair %lld: traceback inconsistent with its sequences", hits[e].pair);
+	return window_words(h, w, co.off, n, co.cap, co.words);
 }
 
 extern "C" int at_allpairs_hits(at_handle *h, int mode, int64_t nreads,
@@ -3792,18 +3596,16 @@ extern "C" int at_allpairs_hits(at_handle *h, int mode, int64_t nreads,
                                 int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
                                 uint32_t *out_cigar, int64_t cigar_cap)
 {
-	int rc = check_allpairs_args(h, "at_allpairs_hits", mode, nreads, first_pair, npairs);
-	if (rc) return rc;
-	if (h->comm) return fail(h, AT_ERR_DOMAIN, "at_allpairs_hits: one GPU only (this handle belongs to a multi-process job)");
+	const char *who = "at_allpairs_hits";
+	int rc = check_allpairs_args(h, who, mode, nreads, first_pair, npairs);
+	if (rc || (rc = check_one_gpu(h, who))) return rc;
 	if (hit_cap < 0 || cigar_cap < 0) return fail(h, AT_ERR_ARG, "at_allpairs_hits: negative capacity");
-	if (flags & ~AT_CIGAR_M) return fail(h, AT_ERR_ARG, "at_allpairs_hits: flags = %d (AT_CIGAR_M or 0)", flags);
-	const bool cg = out_stats || out_ncigar || out_cigar_off || out_cigar;
-	if (cg && (!out_stats || !out_ncigar || !out_cigar_off || (!out_cigar && cigar_cap > 0)))
-		return fail(h, AT_ERR_ARG, "at_allpairs_hits: the CIGAR outputs are either all NULL or all given");
+	const CigarOut co = {out_stats, out_ncigar, out_cigar_off, out_cigar, cigar_cap};
+	if ((rc = check_options(h, who, AT_STRAND_FWD, 0, 0, flags, co, 0, 0))) return rc;   /* (flags and CIGAR outputs) */
+	const bool cg = co.any();
 	if (cg && mode == AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "at_allpairs_hits: edit has no CIGAR here (alignments of edit distances: at_align_batch_cigar)");
-	if (!out_nhits) return fail(h, AT_ERR_ARG, "at_allpairs_hits: NULL argument");
-	if (npairs > 0 && (!seq_blob || !off || !len)) return fail(h, AT_ERR_ARG, "at_allpairs_hits: NULL argument");
-	if (hit_cap > 0 && (!out_pair || !out_a || !out_b || !out_score || !out_end_i || !out_end_j || !out_state))
+	if (!out_nhits || (npairs > 0 && (!seq_blob || !off || !len)) ||
+	    (hit_cap > 0 && (!out_pair || !out_a || !out_b || !out_score || !out_end_i || !out_end_j || !out_state)))
 		return fail(h, AT_ERR_ARG, "at_allpairs_hits: NULL argument");
 	return guarded(h, "at_allpairs_hits", [&]() -> int {
 		*out_nhits = 0;
@@ -3841,21 +3643,16 @@ extern "C" int at_allpairs_hits(at_handle *h, int mode, int64_t nreads,
 		out_cigar_off[0] = 0;
 		if (nh == 0) return (int)AT_OK;
 		/* the traceback pass over the hits, in pieces that keep its descriptor and op buffers moderate */
-		const int64_t piece_hits = 1LL << 20, piece_ops = 1LL << 30;
 		std::vector<int64_t> p_off;
 		std::string tbcfg;
 		for (int64_t a = 0, b; a < nh; a = b) {
 			int64_t ops = 0;
-			for (b = a; b < nh && b - a < piece_hits; ++b) {
-				const int64_t one = (int64_t)len[hits[(size_t)b].a] + len[hits[(size_t)b].b];
-				if (b > a && ops + one > piece_ops) break;
-				ops += one;
-			}
+			b = at::piece_end(a, nh, 1LL << 20, 1LL << 30, [&](int64_t e) { return (int64_t)len[hits[(size_t)e].a] + len[hits[(size_t)e].b]; }, &ops);
 			const int64_t n = b - a, base = out_cigar_off[a];
-			const int64_t room = std::max<int64_t>(0, cigar_cap - base);
 			p_off.assign((size_t)n + 1, 0);
-			rc2 = pairhits_cigars(h, mode, rs, hits.data() + a, n, ops, flags, out_stats + a * 8, out_ncigar + a, p_off.data(),
-			                      room > 0 ? out_cigar + base : nullptr, room, &tbcfg);
+			const int64_t room = std::max<int64_t>(0, cigar_cap - base);
+			const CigarOut piece = {out_stats + a * 8, out_ncigar + a, p_off.data(), room > 0 ? out_cigar + base : nullptr, room};
+			rc2 = pairhits_cigars(h, mode, rs, hits.data() + a, n, ops, flags, piece, &tbcfg);
 			if (rc2) return rc2;
 			for (int64_t e = 1; e <= n; ++e) out_cigar_off[a + e] = base + p_off[(size_t)e];
 		}
