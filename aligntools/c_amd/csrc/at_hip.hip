@@ -105,7 +105,6 @@ struct at_handle {
 	int min_on = 0, min_score = 0;  /* at_set_min_score: all-vs-all overlap scores skip pairs proven below it */
 	int edit_tb = 0;                /* at_set_edit_traceback: edit batches with want_traceback deliver their ops (at_edit_tb.hip.h) */
 	int edit_infix = 0;             /* at_set_edit_infix: AT_MODE_EDIT is the best match of s1 inside s2 (at_infix.hip.h) */
-	int infix_anchor = 0;           /* inside at_scan_hits' window pass only: infix alignments end in (l1, l2) (InfixArgs::anchor_end) */
 	/* device scratch (grow-only) */
 	uint32_t *d_sitemask = nullptr; size_t sitemask_words = 0; int sitemask_for_l2 = -1; bool sitemask_dirty = true;
 	/* the site mask's way up: page-locked buffers used in turn, each with the event behind its copy (ensure_sitemask) */
@@ -116,7 +115,6 @@ struct at_handle {
 	uint32_t *d_ck = nullptr; size_t ck_bytes = 0;   /* two-pass tracebacks with a walk kernel: a launch's checkpoints */
 	bool ck_alloc_failed = false;                    /* ... could not be allocated once: this handle keeps to the rounds inside the sweep's kernel
 	                                                  * for the rest of its life (a later batch would only meet the same shortage) */
-	bool ck_skip = false;                            /* this call only: one work item's checkpoints exceed AT_CK_CAP_MB */
 	unsigned long long *d_queue = nullptr;
 	int last_span = 0;              /* max_len1 + max_len2 of the handle's latest batch: the rendering kernel's hint for its group width */
 	void *d_in = nullptr; size_t in_bytes = 0;
@@ -724,6 +722,15 @@ static int grow(at_handle *h, void **p, size_t *have, size_t need, const char *w
 	return AT_OK;
 }
 
+/* grow() for the handle's buffers of words (d_ws, d_ck) */
+static int grow_words(at_handle *h, uint32_t **p, size_t *have, size_t need, const char *which)
+{
+	void *v = *p;
+	const int rc = grow(h, &v, have, need, which);
+	*p = (uint32_t *)v;
+	return rc;
+}
+
 /* page-locked host memory, grow-only */
 static int grow_pinned(at_handle *h, void **p, size_t *have, size_t need)
 {
@@ -858,10 +865,7 @@ static int plan_launch(at_handle *h, const char *tag, int k, long long nwork, lo
 		const long long cap = env_ll("AT_WS_CAP_MB", 16384) << 20;
 		if (slot_words * 4 > cap) return fail(h, AT_ERR_NOMEM, "one pair needs %lld workspace bytes (cap %lld)", slot_words * 4, cap);
 		grid = std::max(1LL, std::min(grid, cap / (slot_words * 4)));
-		void *p = h->d_ws; size_t have = h->ws_bytes;
-		int rc = grow(h, &p, &have, (size_t)(grid * slot_words * 4), "ws");
-		h->d_ws = (uint32_t *)p; h->ws_bytes = have;
-		if (rc) return rc;
+		if (int rc = grow_words(h, &h->d_ws, &h->ws_bytes, (size_t)(grid * slot_words * 4), "ws")) return rc;
 		pl->ws = h->d_ws;
 	}
 	pl->grid = grid;
@@ -872,15 +876,41 @@ static int plan_launch(at_handle *h, const char *tag, int k, long long nwork, lo
 	return AT_OK;
 }
 
-static int align_device(at_handle *h, int mode, int64_t npairs,
-                        const uint32_t *d_seq, int bits,
-                        const int64_t *d_woff1, const int32_t *d_len1,
-                        const int64_t *d_woff2, const int32_t *d_len2,
-                        int32_t max_len1, int32_t max_len2, int uniform_shape, int want_traceback,
-                        int32_t *d_score, int32_t *d_end_i, int32_t *d_end_j, int32_t *d_state,
-                        uint8_t *d_ops, const int64_t *d_ops_off, int32_t *d_nops, void *stream_,
-                        int64_t ap_n, int64_t ap_first, const int *d_order = nullptr, int rag = 0,
-                        const int *only_if = nullptr, int only_val = 0);
+/* One batch launch, as align_device takes it.  Every entry fills one by field name; the per-call settings start as the handle's
+ * and an entry that needs others (the scans' window pass, at_allpairs_hits) overrides them HERE: the handle is not written while
+ * a call runs (its helper handles run chunks side by side), ck_alloc_failed -- a fact about the handle's lifetime -- excepted */
+struct BatchReq {
+	int mode = 0;
+	int64_t npairs = 0;
+	const uint32_t *d_seq = nullptr;
+	int bits = 2;
+	const int64_t *d_woff1 = nullptr, *d_woff2 = nullptr;
+	const int32_t *d_len1 = nullptr, *d_len2 = nullptr;
+	int32_t max_len1 = 0, max_len2 = 0;
+	int uniform_shape = 0, want_traceback = 0;
+	int32_t *d_score = nullptr, *d_end_i = nullptr, *d_end_j = nullptr, *d_state = nullptr;
+	uint8_t *d_ops = nullptr;
+	const int64_t *d_ops_off = nullptr;
+	int32_t *d_nops = nullptr;
+	hipStream_t stream = nullptr;
+	int64_t ap_n = 0, ap_first = 0;           /* all-vs-all: pair p of the launch is pair ap_first + p of the triangle over ap_n reads */
+	const int *d_order = nullptr;             /* the processing order of a ragged batch */
+	int rag = 0;                              /* ragged frames: their group width (the host entry) */
+	const int *only_if = nullptr;             /* the launch is a no-op unless *only_if == only_val (auto-uniform) */
+	int only_val = 0;
+	/* ---- per-call settings ---- */
+	int edit_infix = 0, edit_tb = 0;          /* at_set_edit_infix, at_set_edit_traceback */
+	int infix_anchor = 0;                     /* at_scan_hits' window pass: infix alignments end in (l1, l2) (InfixArgs::anchor_end) */
+	int min_on = 0, min_score = 0;            /* at_set_min_score */
+	const char *no_walk = nullptr;            /* no walk kernel for this call: the reason, as at_last_config says it */
+
+	explicit BatchReq(const at_handle *h)
+	{
+		if (h) { edit_infix = h->edit_infix; edit_tb = h->edit_tb; min_on = h->min_on; min_score = h->min_score; }
+	}
+};
+
+static int align_device(at_handle *h, const BatchReq &r);
 
 extern "C" int at_align_batch_device(at_handle *h, int mode, int64_t npairs,
                                      const uint32_t *d_seq, int bits,
@@ -891,8 +921,13 @@ extern "C" int at_align_batch_device(at_handle *h, int mode, int64_t npairs,
                                      uint8_t *d_ops, const int64_t *d_ops_off, int32_t *d_nops, void *stream_)
 {
 	if (!d_woff2 || !d_len2) return fail(h, AT_ERR_ARG, "NULL device pointer");
-	return align_device(h, mode, npairs, d_seq, bits, d_woff1, d_len1, d_woff2, d_len2, max_len1, max_len2, uniform_shape,
-	                    want_traceback, d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream_, 0, 0);
+	BatchReq r(h);
+	r.mode = mode; r.npairs = npairs; r.d_seq = d_seq; r.bits = bits; r.stream = (hipStream_t)stream_;
+	r.d_woff1 = d_woff1; r.d_len1 = d_len1; r.d_woff2 = d_woff2; r.d_len2 = d_len2; r.max_len1 = max_len1; r.max_len2 = max_len2;
+	r.uniform_shape = uniform_shape; r.want_traceback = want_traceback;
+	r.d_score = d_score; r.d_end_i = d_end_i; r.d_end_j = d_end_j; r.d_state = d_state;
+	r.d_ops = d_ops; r.d_ops_off = d_ops_off; r.d_nops = d_nops;
+	return align_device(h, r);
 }
 
 extern "C" int at_align_allpairs_device(at_handle *h, int mode, int64_t nreads,
@@ -906,8 +941,14 @@ extern "C" int at_align_allpairs_device(at_handle *h, int mode, int64_t nreads,
 	if (nreads < 2 || first_pair < 0 || npairs < 0 || first_pair + npairs > nreads * (nreads - 1) / 2)
 		return fail(h, AT_ERR_ARG, "all-vs-all: pair range [%lld, +%lld) outside the %lld*(%lld-1)/2 ordered pairs",
 		            (long long)first_pair, (long long)npairs, (long long)nreads, (long long)nreads);
-	return align_device(h, mode, npairs, d_seq, bits, d_woff, d_len, d_woff, d_len, max_len, max_len, 0, want_traceback,
-	                    d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream_, nreads, first_pair);
+	BatchReq r(h);
+	r.mode = mode; r.npairs = npairs; r.d_seq = d_seq; r.bits = bits; r.stream = (hipStream_t)stream_;
+	r.d_woff1 = r.d_woff2 = d_woff; r.d_len1 = r.d_len2 = d_len; r.max_len1 = r.max_len2 = max_len;
+	r.want_traceback = want_traceback;
+	r.d_score = d_score; r.d_end_i = d_end_i; r.d_end_j = d_end_j; r.d_state = d_state;
+	r.d_ops = d_ops; r.d_ops_off = d_ops_off; r.d_nops = d_nops;
+	r.ap_n = nreads; r.ap_first = first_pair;
+	return align_device(h, r);
 }
 
 extern "C" int at_render_batch_device(at_handle *h, int64_t npairs,
@@ -1021,136 +1062,305 @@ extern "C" int at_cigar_batch_device(at_handle *h, int64_t npairs,
 	return AT_OK;
 }
 
-static int align_device(at_handle *h, int mode, int64_t npairs,
-                        const uint32_t *d_seq, int bits,
-                        const int64_t *d_woff1, const int32_t *d_len1,
-                        const int64_t *d_woff2, const int32_t *d_len2,
-                        int32_t max_len1, int32_t max_len2, int uniform_shape, int want_traceback,
-                        int32_t *d_score, int32_t *d_end_i, int32_t *d_end_j, int32_t *d_state,
-                        uint8_t *d_ops, const int64_t *d_ops_off, int32_t *d_nops, void *stream_,
-                        int64_t ap_n, int64_t ap_first, const int *d_order, int rag, const int *only_if, int only_val)
+/* ================ the batch dispatch: align_device, at the end, is the routing order; every kernel family has its
+ * launcher above it.  A launcher reads the request, never the handle's per-call settings ================ */
+
+/* what the register file admits per CU; the runtime's refusal to say is no reason to fail */
+static int occupancy_or_8(const void *fn, size_t lds)
 {
-	if (!h) return fail(nullptr, AT_ERR_ARG, "at_align_batch_device: NULL handle");
-	if (mode < AT_MODE_GLOBAL || mode > AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "unknown mode %d", mode);
-	if (npairs < 0 || max_len1 < 0 || max_len2 < 0) return fail(h, AT_ERR_ARG, "negative size");
-	if (bits != 2 && bits != 8) return fail(h, AT_ERR_ARG, "bits must be 2 or 8");
-	if (npairs == 0) return AT_OK;
-	if (!d_seq || !d_woff1 || !d_len1 || !d_woff2 || !d_len2 || !d_score) return fail(h, AT_ERR_ARG, "NULL device pointer");
-	/* edit alignments (at_set_edit_traceback): batches only -- the all-pairs entries keep the number */
-	const bool edit_tb = want_traceback && mode == AT_MODE_EDIT && h->edit_tb && ap_n == 0;
-	const bool tb = want_traceback && mode != AT_MODE_EDIT;
-	if ((tb || edit_tb) && (!d_ops || !d_ops_off || !d_nops)) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
-	hipStream_t stream = (hipStream_t)stream_;
-	HIP_TRY(h, hipSetDevice(h->device));
-	drop_stale_error();
+	int occ = 0;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64, lds) != hipSuccess || occ <= 0) occ = 8;
+	return occ;
+}
 
-	/* exact-int32 range: real scores stay within 2^24, sentinel at -2^26 (at_sweep.hip.h) */
-	long long maxabs = 0;
-	for (int v : {h->m, h->u, h->o, h->e, h->j}) maxabs = std::max<long long>(maxabs, std::llabs((long long)v));
-	maxabs = std::max<long long>(maxabs, 1);
-	if (maxabs * ((long long)max_len1 + max_len2 + 2) >= (1LL << 24))
-		return fail(h, AT_ERR_RANGE, "scores may exceed the exact range: max|param|=%lld, l1+l2=%lld", maxabs,
-		            (long long)max_len1 + max_len2);
+/* what every bit-parallel kernel takes from a request (the queue follows ensure_queue) */
+static at::MyersArgs myers_args(const BatchReq &r)
+{
+	at::MyersArgs m;
+	memset(&m, 0, sizeof m);
+	m.npairs = r.npairs; m.seq = r.d_seq;
+	m.woff1 = (const long long *)r.d_woff1; m.woff2 = (const long long *)r.d_woff2; m.len1 = r.d_len1; m.len2 = r.d_len2;
+	m.max_l1 = r.max_len1; m.max_l2 = r.max_len2;
+	m.score = r.d_score; m.end_i = r.d_end_i; m.end_j = r.d_end_j; m.state = r.d_state; m.nops = r.d_nops;
+	m.order = r.d_order;
+	m.ap_n = r.ap_n; m.ap_first = r.ap_first;
+	return m;
+}
 
-	h->last_span = max_len1 + max_len2;
-	const int kmode = mode == AT_MODE_GLOBAL ? at::K_GLOBAL : mode == AT_MODE_LOCAL ? at::K_LOCAL
-	                : mode == AT_MODE_FIT ? (h->use_jump ? at::K_FITJ : at::K_FIT)
-	                : mode == AT_MODE_OVERLAP ? at::K_OVERLAP : at::K_EDIT;
+/* The slab of the two op-list edit paths (at_edit_tb, at_infix): one column is W words x 2 planes x 64 lanes per work item, bounded
+ * like the pointer slots of plan_launch.  slab_size refuses a work item over the cap (`what` opens the text); slab_grid sizes the
+ * grid by the occupancy and the cap and grows d_ws */
+struct SlabPlan { long long slab_words = 0, cap = 0, per_cu = 0, grid = 0; };
+static int slab_size(at_handle *h, const char *what, const BatchReq &r, int w, SlabPlan *sp)
+{
+	sp->slab_words = (long long)std::max(r.max_len2, 1) * w * 128;
+	sp->cap = env_ll("AT_WS_CAP_MB", 16384) << 20;
+	if (sp->slab_words * 4 > sp->cap)
+		return fail(h, AT_ERR_NOMEM, "%s: one work item needs %lld workspace bytes (cap %lld)", what, sp->slab_words * 4, sp->cap);
+	return AT_OK;
+}
+static int slab_grid(at_handle *h, const BatchReq &r, int occ, SlabPlan *sp)
+{
+	sp->per_cu = std::max(1LL, std::min<long long>(occ, env_ll("AT_WAVES_PER_CU", 16)));
+	sp->grid = std::max(1LL, std::min<long long>(std::min<long long>((r.npairs + 63) / 64, sp->per_cu * h->ncu), sp->cap / (sp->slab_words * 4)));
+	return grow_words(h, &h->d_ws, &h->ws_bytes, (size_t)(sp->grid * sp->slab_words * 4), "ws");
+}
 
-	/* ---- edit infix mode (at_set_edit_infix): the best match of s1 inside s2 on the bit-parallel path with a zero top border
-	 * (at_infix.hip.h), with the op lists when edit alignments are on and wanted.  Outside the domain the call fails: a global
-	 * distance under an infix setting would be a wrong answer ---- */
-	if (mode == AT_MODE_EDIT && h->edit_infix) {
-		const bool itb = want_traceback && h->edit_tb;
-		const size_t lds = at::myers_window_bytes(64, max_len2);   /* the 64 s2 windows of a wavefront */
-		if (ap_n > 0) return fail(h, AT_ERR_DOMAIN, "edit infix mode: no all-vs-all (pair lists and searches only)");
-		if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "edit infix mode needs the unit mismatch cost: u = %d, not 1", h->u);
-		if (bits != 2) return fail(h, AT_ERR_DOMAIN, "edit infix mode needs a 2-bit batch: some base is not one of ACGT");
-		if (max_len1 > 1024) return fail(h, AT_ERR_DOMAIN, "edit infix mode: max_len1 = %d exceeds 1024", max_len1);
-		if (lds > 60 * 1024) return fail(h, AT_ERR_DOMAIN, "edit infix mode: max_len2 = %d exceeds 3792 (64 windows of packed words in 60 KB of LDS)", max_len2);
-		if (rag || only_if) return fail(h, AT_ERR_ARG, "edit infix mode: not a packed launch");
-		const int w = at::class_rows(at::kMyersLaneWords, max_len1);
-		at_infix_fn fn = at_pick_infix(w, itb ? 1 : 0);
-		if (!fn) return fail(h, AT_ERR_ARG, "no edit infix kernel for %d words per lane", w);
-		int occ = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, 64, lds) != hipSuccess || occ <= 0) occ = 8;
-		at::InfixArgs ia;
-		memset(&ia, 0, sizeof ia);
-		ia.m.npairs = npairs; ia.m.seq = d_seq;
-		ia.m.woff1 = (const long long *)d_woff1; ia.m.woff2 = (const long long *)d_woff2; ia.m.len1 = d_len1; ia.m.len2 = d_len2;
-		ia.m.max_l1 = max_len1; ia.m.max_l2 = max_len2;
-		ia.m.score = d_score; ia.m.end_i = d_end_i; ia.m.end_j = d_end_j; ia.m.state = d_state; ia.m.nops = d_nops;
-		ia.m.order = d_order;
-		if (!itb) {
-			/* sized as the number-only launch of at_myers, one alignment per lane */
-			const long long grid = std::max(1LL, std::min<long long>((npairs + 63) / 64, (long long)occ * h->ncu));
-			if (int rcq = ensure_queue(h, stream)) return rcq;
-			ia.m.queue = h->d_queue;
-			hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, stream, ia);
-			HIP_TRY(h, hipGetLastError());
-			snprintf(h->cfg, sizeof h->cfg, "myers-infix bits=2 words/lane=%d (64 pairs/wave) lds=%zuB waves/cu<=%d grid=%lld", w, lds, occ, grid);
-			return AT_OK;
-		}
-		if (!d_ops || !d_ops_off || !d_nops) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
-		/* the slab of at_edit_tb: one column is W words x 2 planes x 64 lanes; the same caps */
-		const long long slab_words = (long long)std::max(max_len2, 1) * w * 128;
-		const long long cap = env_ll("AT_WS_CAP_MB", 16384) << 20;
-		if (slab_words * 4 > cap)
-			return fail(h, AT_ERR_NOMEM, "edit infix alignments: one work item needs %lld workspace bytes (cap %lld)", slab_words * 4, cap);
-		const long long per_cu = std::max(1LL, std::min<long long>(occ, env_ll("AT_WAVES_PER_CU", 16)));
-		const long long grid = std::max(1LL, std::min<long long>(std::min<long long>((npairs + 63) / 64, per_cu * h->ncu), cap / (slab_words * 4)));
-		{
-			void *p = h->d_ws; size_t have = h->ws_bytes;
-			int rc = grow(h, &p, &have, (size_t)(grid * slab_words * 4), "ws");
-			h->d_ws = (uint32_t *)p; h->ws_bytes = have;
-			if (rc) return rc;
-		}
-		ia.ops = d_ops; ia.ops_off = (const long long *)d_ops_off;
-		ia.slab = h->d_ws; ia.slab_words = slab_words;
-		ia.anchor_end = h->infix_anchor;
-		if (int rcq = ensure_queue(h, stream)) return rcq;
-		ia.m.queue = h->d_queue;
-		hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, stream, ia);
-		HIP_TRY(h, hipGetLastError());
+/* ---- edit infix mode (at_set_edit_infix): the best match of s1 inside s2 on the bit-parallel path with a zero top border
+ * (at_infix.hip.h), with the op lists when edit alignments are on and wanted.  Outside the domain the call fails: a global
+ * distance under an infix setting would be a wrong answer ---- */
+static int launch_infix(at_handle *h, const BatchReq &r)
+{
+	const bool itb = r.want_traceback && r.edit_tb;
+	const size_t lds = at::myers_window_bytes(64, r.max_len2);   /* the 64 s2 windows of a wavefront */
+	if (r.ap_n > 0) return fail(h, AT_ERR_DOMAIN, "edit infix mode: no all-vs-all (pair lists and searches only)");
+	if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "edit infix mode needs the unit mismatch cost: u = %d, not 1", h->u);
+	if (r.bits != 2) return fail(h, AT_ERR_DOMAIN, "edit infix mode needs a 2-bit batch: some base is not one of ACGT");
+	if (r.max_len1 > 1024) return fail(h, AT_ERR_DOMAIN, "edit infix mode: max_len1 = %d exceeds 1024", r.max_len1);
+	if (lds > 60 * 1024) return fail(h, AT_ERR_DOMAIN, "edit infix mode: max_len2 = %d exceeds 3792 (64 windows of packed words in 60 KB of LDS)", r.max_len2);
+	if (r.rag || r.only_if) return fail(h, AT_ERR_ARG, "edit infix mode: not a packed launch");
+	const int w = at::class_rows(at::kMyersLaneWords, r.max_len1);
+	at_infix_fn fn = at_pick_infix(w, itb ? 1 : 0);
+	if (!fn) return fail(h, AT_ERR_ARG, "no edit infix kernel for %d words per lane", w);
+	const int occ = occupancy_or_8((const void *)fn, lds);
+	at::InfixArgs ia;
+	memset(&ia, 0, sizeof ia);
+	ia.m = myers_args(r);
+	SlabPlan sp;
+	if (itb) {
+		/* the slab of at_edit_tb, the same caps (the op buffers are there: align_device has looked) */
+		int rc = slab_size(h, "edit infix alignments", r, w, &sp);
+		if (!rc) rc = slab_grid(h, r, occ, &sp);
+		if (rc) return rc;
+		ia.ops = r.d_ops; ia.ops_off = (const long long *)r.d_ops_off;
+		ia.slab = h->d_ws; ia.slab_words = sp.slab_words;
+		ia.anchor_end = r.infix_anchor;
+	} else {
+		/* sized as the number-only launch of at_myers, one alignment per lane */
+		sp.grid = std::max(1LL, std::min<long long>((r.npairs + 63) / 64, (long long)occ * h->ncu));
+	}
+	if (int rcq = ensure_queue(h, r.stream)) return rcq;
+	ia.m.queue = h->d_queue;
+	hipLaunchKernelGGL(fn, dim3((unsigned)sp.grid), dim3(64), lds, r.stream, ia);
+	HIP_TRY(h, hipGetLastError());
+	if (itb)
 		snprintf(h->cfg, sizeof h->cfg, "myers-infix-tb bits=2 words/lane=%d (64 pairs/wave) lds=%zuB slab=%lldB waves/cu<=%lld grid=%lld", w, lds,
-		         slab_words * 4, per_cu, grid);
-		return AT_OK;
-	}
+		         sp.slab_words * 4, sp.per_cu, sp.grid);
+	else
+		snprintf(h->cfg, sizeof h->cfg, "myers-infix bits=2 words/lane=%d (64 pairs/wave) lds=%zuB waves/cu<=%d grid=%lld", w, lds, occ, sp.grid);
+	return AT_OK;
+}
 
-	/* ---- packed int16 path: uniform shape, scores provably within 16 bits ---- */
-	/* scores x16 with nibble pointers when they fit (|score| < 2048), else x4 with byte pointers (|score| < 8192) */
-	int thresh16 = 0, ts = 0;
-	if (!uniform_shape && !rag && !only_if && ap_n == 0 && npairs >= 4096 && !d_order && kmode <= at::K_FITJ &&
-	    env_ll("AT_AUTO_UNIFORM", 1) && (bits == 8 || scores_fit_byte(h, mode)) &&
-	    packed_ok(h, mode, bits, max_len1, max_len2, 4, &thresh16)) {
-		/* The caller did not promise one shape, but the batch may well have one (fixed-length reads against fixed
-		 * windows).  The lengths live on the device and this entry is asynchronous, so the device decides: a check
-		 * kernel leaves 1 in a flag if every pair is max_len1 x max_len2, and the packed and the int32 launch are both
-		 * queued, each of them a no-op unless the flag names it. */
-		int *flag = h->d_rflag + 8;
-		HIP_TRY(h, hipMemsetAsync(flag, 0xff, 4, stream));
-		const unsigned cg = (unsigned)std::min<int64_t>((npairs + 255) / 256, 4LL * h->ncu);
-		hipLaunchKernelGGL(at::at_check_uniform, dim3(cg), dim3(256), 0, stream, d_len1, d_len2, (long long)npairs, max_len1, max_len2, flag);
-		int rc = align_device(h, mode, npairs, d_seq, bits, d_woff1, d_len1, d_woff2, d_len2, max_len1, max_len2, 1, want_traceback,
-		                      d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream_, 0, 0, nullptr, 0, flag, -1);
-		if (rc) return rc;
-		std::string packed_cfg = h->cfg;
-		rc = align_device(h, mode, npairs, d_seq, bits, d_woff1, d_len1, d_woff2, d_len2, max_len1, max_len2, 0, want_traceback,
-		                  d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream_, 0, 0, nullptr, 0, flag, 0);
-		if (rc) return rc;
-		snprintf(h->cfg, sizeof h->cfg, "auto: [%.140s] if every pair is %dx%d, else [%.120s]", packed_cfg.c_str(), max_len1, max_len2,
-		         std::string(h->cfg).c_str());
+/* ---- edit alignments (at_set_edit_traceback): the bit-parallel fill keeps its columns, the same wavefront walks them
+ * (at_edit_tb.hip.h).  Outside the domain the call fails: no silent fall back to the number alone ---- */
+static int launch_edit_tb(at_handle *h, const BatchReq &r)
+{
+	const size_t lds = at::myers_window_bytes(64, r.max_len2);   /* the 64 s2 windows of a wavefront */
+	if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "edit alignments need the unit mismatch cost: u = %d, not 1", h->u);
+	if (r.bits != 2) return fail(h, AT_ERR_DOMAIN, "edit alignments need a 2-bit batch: some base is not one of ACGT");
+	if (r.max_len1 > 1024) return fail(h, AT_ERR_DOMAIN, "edit alignments: max_len1 = %d exceeds 1024", r.max_len1);
+	if (lds > 60 * 1024) return fail(h, AT_ERR_DOMAIN, "edit alignments: max_len2 = %d exceeds 3792 (64 windows of packed words in 60 KB of LDS)", r.max_len2);
+	const int w = at::class_rows(at::kMyersLaneWords, r.max_len1);
+	at_edit_tb_fn fn = at_pick_edit_tb(w);
+	if (!fn) return fail(h, AT_ERR_ARG, "no edit alignment kernel for %d words per lane", w);
+	SlabPlan sp;
+	int rc = slab_size(h, "edit alignments", r, w, &sp);
+	if (!rc) rc = slab_grid(h, r, occupancy_or_8((const void *)fn, lds), &sp);
+	if (rc) return rc;
+	at::EditTbArgs ea;
+	memset(&ea, 0, sizeof ea);
+	ea.m = myers_args(r);
+	ea.ops = r.d_ops; ea.ops_off = (const long long *)r.d_ops_off;
+	ea.slab = h->d_ws; ea.slab_words = sp.slab_words;
+	if (int rcq = ensure_queue(h, r.stream)) return rcq;
+	ea.m.queue = h->d_queue;
+	hipLaunchKernelGGL(fn, dim3((unsigned)sp.grid), dim3(64), lds, r.stream, ea);
+	HIP_TRY(h, hipGetLastError());
+	snprintf(h->cfg, sizeof h->cfg, "myers-tb bits=2 words/lane=%d (64 pairs/wave) lds=%zuB slab=%lldB waves/cu<=%lld grid=%lld", w, lds,
+	         sp.slab_words * 4, sp.per_cu, sp.grid);
+	return AT_OK;
+}
+
+/* ---- edit distance with unit mismatch cost: bit-parallel kernel (at_myers.hip.h), any mix of lengths ---- */
+/* (two s2 windows of a wavefront must fit 60 KB of LDS, or the cell-by-cell kernel takes the batch) */
+static bool myers_takes(const at_handle *h, const BatchReq &r, int kmode)
+{
+	return kmode == at::K_EDIT && h->u == 1 && r.bits == 2 && r.max_len1 <= 32768 && at::myers_window_bytes(2, r.max_len2) <= 60 * 1024 &&
+	       env_ll("AT_MYERS", 1);
+}
+
+static int launch_myers(at_handle *h, const BatchReq &r)
+{
+	/* (bytes of LDS for the s2 windows of the n alignments of a wavefront) */
+	auto myers_windows = [&](int n) { return at::myers_window_bytes(n, r.max_len2); };
+	/* lanes per alignment and words per lane: reads of up to AT_MYERS_LANE_MAX (1 024) bases one alignment per LANE -- 5, 8, 16 or 32
+	 * words, 64 s2 windows in LDS (second sequences of up to ~3 500 bases) -- else 32 lanes; the 16- and 32-word forms only for batches
+	 * of AT_MYERS_LANE_MIN_PAIRS (16 384: one wavefront per CU) and more -- 10 000 pairs of 1 000 x 1 000 are 157 wavefronts on 1 024
+	 * SIMDs, 19 TCUPS against 31 on 32-lane groups; 131 072 of them 43 against 36.  AT_MYERS_GROUP = 8: the round-2 form, eight lanes
+	 * for reads of up to 256 bases and 32 beyond (A/B) */
+	const long long lane_max = env_ll("AT_MYERS_LANE_MAX", 1024);
+	const bool per_lane = r.max_len1 <= lane_max && r.max_len1 <= 1024 && myers_windows(64) <= 60 * 1024 &&
+	                      (r.max_len1 <= 256 || r.npairs >= env_ll("AT_MYERS_LANE_MIN_PAIRS", 16384)) && env_ll("AT_MYERS_GROUP", 1) == 1;
+	const int g = per_lane ? 1 : r.max_len1 <= 256 && myers_windows(8) <= 60 * 1024 ? 8 : 32;
+	const int w = per_lane ? at::class_rows(at::kMyersLaneWords, r.max_len1) : at::class_rows(at::kMyersGroupWords, r.max_len1);
+	at_myers_fn fn = at_pick_myers(w, g);
+	const int per_wave = 64 / g;
+	at::MyersArgs m = myers_args(r);
+	if (int rcq = ensure_queue(h, r.stream)) return rcq;
+	m.queue = h->d_queue;
+	const size_t lds = myers_windows(per_wave);
+	if (lds > 60 * 1024) return fail(h, AT_ERR_RANGE, "second sequence too long for the bit-parallel kernel's LDS window");
+	const int occ = occupancy_or_8((const void *)fn, lds);
+	const long long grid = std::max(1LL, std::min<long long>((r.npairs + per_wave - 1) / per_wave, (long long)occ * h->ncu));
+	hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, r.stream, m);
+	HIP_TRY(h, hipGetLastError());
+	snprintf(h->cfg, sizeof h->cfg, "myers bits=2 words/lane=%d %dx%d-lane groups (%d pairs/wave) lds=%zuB waves/cu<=%d grid=%lld", w, per_wave, g, per_wave,
+	         lds, occ, grid);
+	return AT_OK;
+}
+
+/* ---- all-vs-all overlap scores with a threshold (at_set_min_score): the bit-parallel filter (at_myers.hip.h, SEMI) bounds every
+ * pair's score from above at a seventh of the sweep's cost; only pairs whose bound reaches the threshold are swept.  The filter
+ * leaves (upper bound, state 0) in every pair's result slot and the candidates' indices in a list; the int32 sweep takes the
+ * list and its length from the device and overwrites the candidates' slots with exact results.  No host round trip.
+ * Where the filter applies, *cand_order and *cand_count are that list and its length on the device and `note` opens the
+ * sweep's at_last_config; elsewhere all three stay as they are ---- */
+static int overlap_filter(at_handle *h, const BatchReq &r, int kmode, bool tb, const int **cand_order, const int **cand_count, char (&note)[96])
+{
+	if (!(kmode == at::K_OVERLAP && !tb && r.ap_n > 0 && r.min_on && !r.d_order && !r.only_if && r.bits == 2 && r.max_len1 >= 1 && r.max_len1 <= 1024 &&
+	      r.npairs < (1LL << 31) - 64 && env_ll("AT_OVERLAP_FILTER", 1)))
 		return AT_OK;
+	/* 2 score <= 2 m b - (2 c - m) D', c = min(m - u, m / 2 - o): needs m >= 0 and 2 c > m */
+	const long long k2 = std::min<long long>(2LL * (h->m - h->u), (long long)h->m - 2LL * h->o) - h->m;
+	const int w = at::class_rows(at::kMyersLaneWords, r.max_len1);
+	at_myers_fn ffn = at_pick_myers_semi(w);
+	const size_t lds = at::myers_window_bytes(64, r.max_len2);
+	if (!(h->m >= 0 && k2 > 0 && k2 < 4096 && h->m < 4096 && lds <= 60 * 1024 && ffn)) return AT_OK;
+	int rc = grow(h, &h->d_order, &h->order_bytes, ((size_t)r.npairs + 64) * 4);
+	if (rc) return rc;
+	int *cand = (int *)h->d_order, *count = cand + ((r.npairs + 15) & ~15LL);
+	HIP_TRY(h, hipMemsetAsync(count, 0, 4, r.stream));
+	at::MyersArgs m = myers_args(r);
+	m.nops = nullptr;   /* (scores only: the bound has no op counts) */
+	m.semi_m2 = 2 * h->m; m.semi_k = (int)k2; m.semi_min2 = (int)std::max<long long>(std::min<long long>(2LL * r.min_score, INT32_MAX), INT32_MIN);
+	m.cand_order = cand; m.cand_count = count;
+	if (int rcq = ensure_queue(h, r.stream)) return rcq;
+	m.queue = h->d_queue;
+	const int occ = occupancy_or_8((const void *)ffn, lds);
+	const long long fgrid = std::max(1LL, std::min<long long>((r.npairs + 63) / 64, (long long)occ * h->ncu));
+	hipLaunchKernelGGL(ffn, dim3((unsigned)fgrid), dim3(64), lds, r.stream, m);
+	HIP_TRY(h, hipGetLastError());
+	*cand_order = cand; *cand_count = count;
+	snprintf(note, sizeof note, "overlap filter (bit-parallel bound, %d words/lane, min score %d) + ", w, r.min_score);
+	return AT_OK;
+}
+
+/* ---- the int32 sweep: every mode, any mix of lengths.  d_order: the request's, or the overlap filter's candidates with their
+ * count in *npairs_dev and the filter's note ---- */
+static int launch_int32(at_handle *h, const BatchReq &r, int kmode, bool tb, const int *d_order, const int *npairs_dev, const char *filter_note)
+{
+	/* the int32 kernels read 2-bit scores from a byte LUT (the packed ones from a 16-bit one) */
+	if (r.bits == 2 && !scores_fit_byte(h, r.mode))
+		return fail(h, AT_ERR_RANGE, "the int32 2-bit kernels need |16*score| <= 127 (m=%d u=%d o=%d): pack the batch with bits=8", h->m, h->u, h->o);
+	const Layout L = layout_for(kmode, r.bits, tb, r.max_len1, r.max_len2);
+	if (L.words >= (1LL << 30)) return fail(h, AT_ERR_RANGE, "pair too large: %lld workspace words", L.words);
+	SweepArgs a;
+	memset(&a, 0, sizeof a);
+	a.npairs = r.npairs;
+	a.seq = r.d_seq;
+	a.woff1 = (const long long *)r.d_woff1; a.len1 = r.d_len1;
+	a.woff2 = (const long long *)r.d_woff2; a.len2 = r.d_len2;
+	a.m16 = h->m * 16; a.u16 = h->u * 16; a.o16 = h->o * 16; a.e16 = h->e * 16; a.g16 = h->j * 16;
+	a.u_raw = h->u;
+	a.score = r.d_score; a.end_i = r.d_end_i; a.end_j = r.d_end_j; a.state = r.d_state;
+	a.ops = r.d_ops; a.ops_off = (const long long *)r.d_ops_off; a.nops = r.d_nops;
+	a.off_bound = L.off_bound; a.ptr_lanes = L.ptr_lanes; a.off_sm = L.off_sm; a.nsm = L.nsm;
+	a.ap_n = r.ap_n; a.ap_first = r.ap_first; a.order = d_order;
+	a.only_if = r.only_if; a.only_val = r.only_val;
+	a.npairs_dev = npairs_dev;
+	if (kmode == at::K_FITJ) {
+		int rc = ensure_sitemask(h, r.max_len2, r.stream);
+		if (rc) return rc;
+		a.sitemask = h->d_sitemask;
 	}
-	if ((uniform_shape || rag) && ap_n == 0) {
-		if (packed_ok(h, mode, bits, max_len1, max_len2, 4, &thresh16)) ts = 4;
-		else if ((!rag || kmode == at::K_OVERLAP) && packed_ok(h, mode, bits, max_len1, max_len2, 2, &thresh16)) ts = 2;
+	Plan pl;
+	char tag[32];
+	snprintf(tag, sizeof tag, "int32 bits=%d", r.bits);
+	int rc = plan_launch(h, tag, L.k, r.npairs, L.off_ptr, L.words - L.off_ptr, &pl, r.stream, [&](int st) {
+		return (const void *)(r.bits == 2 ? at_pick32_b2(kmode, L.k, st, tb) : at_pick32_b8(kmode, L.k, st, tb));
+	});
+	if (rc) return rc;
+	a.off_ptr = pl.off_ptr; a.ws = pl.ws; a.ws_slot_words = pl.slot_words; a.queue = h->d_queue;
+	a.max_l1 = r.max_len1; a.max_l2 = r.max_len2;
+	at_sweep_fn fn = r.bits == 2 ? at_pick32_b2(kmode, L.k, pl.store, tb) : at_pick32_b8(kmode, L.k, pl.store, tb);
+	if (pl.dyn_lds > 48 * 1024)
+		HIP_TRY(h, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.dyn_lds));
+	hipLaunchKernelGGL(fn, dim3((unsigned)pl.grid), dim3(64), pl.dyn_lds, r.stream, a);
+	HIP_TRY(h, hipGetLastError());
+	if (filter_note[0]) {
+		const std::string tail = h->cfg;
+		snprintf(h->cfg, sizeof h->cfg, "%s%.200s", filter_note, tail.c_str());
+	}
+	return AT_OK;
+}
+
+/* ---- auto-uniform: the caller did not promise one shape, but the batch may well have one (fixed-length reads against fixed
+ * windows).  The lengths live on the device and this entry is asynchronous, so the device decides: a check kernel leaves 1 in a
+ * flag if every pair is max_len1 x max_len2, and the packed and the int32 launch are both queued, each of them a no-op unless the
+ * flag names it ---- */
+static bool auto_uniform_applies(const at_handle *h, const BatchReq &r, int kmode)
+{
+	int thresh16 = 0;
+	return !r.uniform_shape && !r.rag && !r.only_if && r.ap_n == 0 && r.npairs >= 4096 && !r.d_order && kmode <= at::K_FITJ &&
+	       env_ll("AT_AUTO_UNIFORM", 1) && (r.bits == 8 || scores_fit_byte(h, r.mode)) &&
+	       packed_ok(h, r.mode, r.bits, r.max_len1, r.max_len2, 4, &thresh16);
+}
+
+static int launch_auto_uniform(at_handle *h, const BatchReq &r)
+{
+	int *flag = h->d_rflag + 8;
+	HIP_TRY(h, hipMemsetAsync(flag, 0xff, 4, r.stream));
+	const unsigned cg = (unsigned)std::min<int64_t>((r.npairs + 255) / 256, 4LL * h->ncu);
+	hipLaunchKernelGGL(at::at_check_uniform, dim3(cg), dim3(256), 0, r.stream, r.d_len1, r.d_len2, (long long)r.npairs, r.max_len1, r.max_len2, flag);
+	BatchReq guarded_req = r;
+	guarded_req.only_if = flag;
+	guarded_req.uniform_shape = 1; guarded_req.only_val = -1;
+	int rc = align_device(h, guarded_req);
+	if (rc) return rc;
+	const std::string packed_cfg = h->cfg;
+	guarded_req.uniform_shape = 0; guarded_req.only_val = 0;
+	rc = align_device(h, guarded_req);
+	if (rc) return rc;
+	snprintf(h->cfg, sizeof h->cfg, "auto: [%.140s] if every pair is %dx%d, else [%.120s]", packed_cfg.c_str(), r.max_len1, r.max_len2,
+	         std::string(h->cfg).c_str());
+	return AT_OK;
+}
+
+/* ---- packed int16 path: uniform shape (or ragged frames), scores provably within 16 bits ---- */
+/* what route_packed decides: ts = 0 -- not this path */
+struct Packed16 {
+	int ts = 0;            /* scores x16 with nibble pointers when they fit (|score| < 2048), else x4 with byte pointers (|score| < 8192) */
+	int thresh16 = 0;
+	Layout16 P;
+	bool two_pass = false;
+	int tp_split = 0;      /* pass 2: 0 the rounds inside the sweep's kernel, 1 a walk kernel behind it */
+	const char *ck_note = "";
+};
+
+static int route_packed(at_handle *h, const BatchReq &r, int kmode, bool tb, Packed16 *pk)
+{
+	const int32_t max_len1 = r.max_len1, max_len2 = r.max_len2;
+	const int rag = r.rag, bits = r.bits;
+	int ts = 0;
+	if ((r.uniform_shape || rag) && r.ap_n == 0) {
+		if (packed_ok(h, r.mode, bits, max_len1, max_len2, 4, &pk->thresh16)) ts = 4;
+		else if ((!rag || kmode == at::K_OVERLAP) && packed_ok(h, r.mode, bits, max_len1, max_len2, 2, &pk->thresh16)) ts = 2;
 		/* overlap: the packed kernel exists with pointers only (scores alone: the int32 kernel's 2 instructions per cell win) */
 		if (kmode == at::K_OVERLAP && (!tb || getenv("AT_NO_PACKED_OVERLAP"))) ts = 0;
 	}
-	if (rag && (!ts || (kmode > at::K_FITJ && !(kmode == at::K_OVERLAP && rag == 64)) || max_len1 > at::rag_group_top(rag) || !d_order))
+	if (rag && (!ts || (kmode > at::K_FITJ && !(kmode == at::K_OVERLAP && rag == 64)) || max_len1 > at::rag_group_top(rag) || !r.d_order))
 		return fail(h, AT_ERR_ARG, "ragged packed launch outside its domain");   /* the host entry checks before it asks */
-	Layout16 P;
+	Layout16 &P = pk->P;
 	if (ts) {
 		P = layout16_for(tb, kmode == at::K_FITJ, max_len1, max_len2, ts, rag, kmode == at::K_OVERLAP, kmode,
 		                 rag && kmode == at::K_OVERLAP ? at::class_rows(at::kClassOvl, max_len1) : 0);   /* (ragged overlap: one strip) */
@@ -1159,13 +1369,13 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		 * packed vs 2.00 TCUPS int32 for a lone launch, 2.70 vs 2.13 with launches in flight; 61k pairs: 2.70 vs 2.19.)  Not a ragged launch:
 		 * its order is padded with ~index repeats, which only the packed kernels understand */
 		const double min_rounds = getenv("AT_PACKED_MIN_ROUNDS") ? atof(getenv("AT_PACKED_MIN_ROUNDS")) : 1.0;
-		if (!rag && P.g == 64 && (double)((npairs + 1) / 2) < min_rounds * 12.0 * h->ncu) ts = 0;
+		if (!rag && P.g == 64 && (double)((r.npairs + 1) / 2) < min_rounds * 12.0 * h->ncu) ts = 0;
 		/* the packed kernels index their slot with 24-bit multiplies: a pair whose slot would not fit takes the int32 kernel */
 		if (P.words >= (1LL << 24)) { if (rag) return fail(h, AT_ERR_ARG, "ragged packed launch outside its domain (slot too large)"); ts = 0; }
 		/* no packed kernel for the storage class this shape needs (the 16- and 32-lane groups have no all-HBM variant:
 		 * a 150-base read against a second sequence of more than ~4 000 bases): the int32 kernel takes any length */
 		Layout16 PTq = P;
-		const bool tailq = !rag && !only_if && P.g <= 16 && kmode != at::K_OVERLAP && env_ll("AT_TAIL_SPLIT", 1);
+		const bool tailq = !rag && !r.only_if && P.g <= 16 && kmode != at::K_OVERLAP && env_ll("AT_TAIL_SPLIT", 1);
 		if (tailq) PTq = layout16_for(tb, kmode == at::K_FITJ, max_len1, max_len2, ts, at::AT_TAIL_G, false, kmode, at::at_tail_k(P.g, P.k));
 		if (ts && !packed16_kernel_exists(kmode, P, tb, ts, bits, rag, tailq ? &PTq : nullptr)) {
 			if (rag) return fail(h, AT_ERR_ARG, "ragged packed launch outside its domain (frame too long for LDS)");
@@ -1176,9 +1386,6 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 	 * By default where that wins -- the 64-lane groups with 16 rows per lane (reads of 609 .. 1 024 bases: the one-pass kernels hold 4 rows
 	 * per lane there and need four strips); AT_TWO_PASS=2: wherever a CK kernel exists (the 8-lane groups x 19 rows lose: C2 -7 %, C4
 	 * -28 %, profiles/r04/two_pass_ab.txt), AT_TWO_PASS=0: never (A/B runs) */
-	bool two_pass = false;
-	int tp_split = 0;   /* pass 2: 0 the rounds inside the sweep's kernel, 1 a walk kernel behind it */
-	const char *ck_note = "";
 	const long long tp_mode = env_ll("AT_TWO_PASS", 1);
 	if (ts && tb && !rag && kmode <= at::K_FITJ && tp_mode) {
 		Layout16 P2 = layout16_for(false, kmode == at::K_FITJ, max_len1, max_len2, ts, 0, false, kmode, 0, 1);
@@ -1189,80 +1396,142 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		const bool narrow_default = P2.g == 8 && tp_split_narrow_default(kmode, max_len1, max_len2);
 		const bool split_default = P2.g == 64 || narrow_default;
 		const bool split_want = env_ll("AT_TP_SPLIT", split_default ? 1 : 0) && at_pick_walk16(kmode, P2.g, P2.k, ts, bits);
-		const int split_req = split_want && !h->ck_alloc_failed && !h->ck_skip ? 1 : 0;
+		const int split_req = split_want && !h->ck_alloc_failed && !r.no_walk ? 1 : 0;
 		/* (the fallback without a checkpoint buffer: the rounds inside the sweep's kernel on the 64-lane groups, the one-pass kernels on the
 		 * 8-lane groups -- at_last_config says so) */
-		if (split_want && !split_req) ck_note = h->ck_skip ? " [one work item's checkpoints exceed AT_CK_CAP_MB: no separate pass 2]"
-		                                                   : " [checkpoint buffer unavailable on this handle: no separate pass 2]";
+		if (split_want && !split_req) pk->ck_note = r.no_walk ? r.no_walk : " [checkpoint buffer unavailable on this handle: no separate pass 2]";
 		if ((P2.g == 64 || tp_mode >= 2 || (split_req && narrow_default)) && (long long)P2.g * P2.k >= max_len1 && at_pick16_tp(kmode, P2.g, P2.k, ts, bits) &&
 		    choose_store(P2.off_ptr, 1, true) == 1) {
-			two_pass = true;
-			tp_split = split_req;
-			if (tp_split) P2 = layout16_for(false, kmode == at::K_FITJ, max_len1, max_len2, ts, 0, false, kmode, 0, 2);
+			pk->two_pass = true;
+			pk->tp_split = split_req;
+			if (pk->tp_split) P2 = layout16_for(false, kmode == at::K_FITJ, max_len1, max_len2, ts, 0, false, kmode, 0, 2);
 			P = P2;
 		}
 	}
-	if (ts) {
-		const int per_wave = 2 * (64 / P.g);
-		/* the sliver's layout (see below) */
-		const bool tail_ok = !rag && !only_if && P.g <= 16 && kmode != at::K_OVERLAP && env_ll("AT_TAIL_SPLIT", 1) &&
-		                     (!tp_split || P.g == 8);   /* (the walk kernels of the 8-lane groups carry their sliver's walks) */
-		Layout16 PT = P;
-		if (tail_ok) PT = layout16_for(tb && !two_pass, kmode == at::K_FITJ, max_len1, max_len2, ts, at::AT_TAIL_G, false, kmode, at::at_tail_k(P.g, P.k), two_pass ? (tp_split ? 2 : 1) : 0);
-		TpLayout tpm{}, tpt{};
-		if (two_pass) { tpm = tp_layout(P, kmode, max_len2, tp_split != 0); tpt = tp_layout(PT, kmode, max_len2, tp_split != 0); }
-		/* split two-pass: the checkpoints of a whole launch live side by side -- C2 225 KB, C3 / C4 1.1 MB per work item -- so a batch is
-		 * swept and walked in pieces whose checkpoints fit AT_CK_CAP_MB (8 192) */
-		int64_t piece = npairs;
-		int64_t brow_words = 0;
-		if (tp_split) {
-			const long long cap = env_ll("AT_CK_CAP_MB", 8192) << 20;
-			brow_words = (tpm.brow_words + 63) & ~63LL;
-			const long long tail_reserve = tail_ok ? 16LL * h->ncu * tpt.words * 4 : 0;
-			const long long items = (cap - tail_reserve - brow_words * 4) / (tpm.words * 4 + 16LL * per_wave);
-			if (items < 1) {
-				/* not even one work item's checkpoints fit the cap: this batch without the walk kernel (nothing has been launched yet) */
-				struct SkipForThisCall {   /* (reset however the call below ends: an exception goes on to guarded()) */
-					at_handle *h;
-					explicit SkipForThisCall(at_handle *hh) : h(hh) { h->ck_skip = true; }
-					~SkipForThisCall() { h->ck_skip = false; }
-				} skip(h);
-				return align_device(h, mode, npairs, d_seq, bits, d_woff1, d_len1, d_woff2, d_len2, max_len1, max_len2, uniform_shape, want_traceback,
-				                    d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream_, ap_n, ap_first, d_order, rag, only_if, only_val);
-			}
-			piece = std::min<int64_t>(npairs, items * per_wave);
-			const long long forced = env_ll("AT_CK_PIECE_PAIRS", 0);   /* (tests: pieces of this many pairs, whatever the cap) */
-			if (forced > 0) piece = std::min<int64_t>(piece, std::max<long long>(1, forced / per_wave) * per_wave);
+	pk->ts = ts;
+	return AT_OK;
+}
+
+/* a walker lane's pointer words of one block, and the walk kernel's LDS (at_walk16.hip.h, walk16_lds_words) */
+static long long walk_lane_words(int kmode, const Layout16 &L)
+{
+	const int cb = at::ck_steps(L.g);
+	return L.k * (cb / 4) + (kmode == at::K_FITJ ? (L.k + 3) / 4 * (cb / 4) : 0);
+}
+static size_t walk_lds(int kmode, const Layout16 &L, bool ptr_in_lds)
+{
+	const int cb = at::ck_steps(L.g), nsm = kmode == at::K_FITJ ? L.nsm : 0;
+	return (size_t)((nsm + 1) / 2 * 2 + (L.k > 16 ? 0 : (cb + 1) * 128) + (ptr_in_lds ? 64 * walk_lane_words(kmode, L) : 0)) * 4;
+}
+
+/* pass 2 of a piece as a kernel of its own, behind the piece's sweep: b the main items, bt the sliver's; *wnote: the walkers note, also
+ * appended to at_last_config */
+static int launch_walk16(at_handle *h, const BatchReq &r, int kmode, const Packed16 &pk, const Layout16 &PT, bool tail_ok,
+                         const Sweep16Args &b, const Sweep16Args &bt, std::string *wnote)
+{
+	const Layout16 &P = pk.P;
+	const int64_t nm = b.npairs, n_tail = bt.npairs;
+	/* the 64-lane groups: teams of lanes per pair of alignments (walk16_team_wave; AT_WALK_TEAMS=0: one walker per half-lane there too) */
+	const bool teams = env_ll("AT_WALK_TEAMS", P.g == 64 ? 1 : 0) && at_pick_walk16(kmode, P.g, P.k, pk.ts, r.bits, 1);
+	at_walk16_fn wf = at_pick_walk16(kmode, P.g, P.k, pk.ts, r.bits, teams);
+	if (!wf) return fail(h, AT_ERR_RANGE, "no walk kernel for %d-lane groups x %d rows", P.g, P.k);
+	const size_t lds = std::max(walk_lds(kmode, P, true), tail_ok ? walk_lds(kmode, PT, true) : 0);
+	if (lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void *)wf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	/* the main units' walkers: one wavefront per 128 alignments (LDS admits four per CU; the others queue).  AT_WALK_WAVES_PER_CU = n:
+	 * at most n per CU, persistent, which refill their halves from the counters behind the sweep's work counter -- fewer
+	 * wavefront-rounds, but a chain of them per wavefront: C4 one launch at a time 1 450 (n = 1) / 1 820 (2) / 2 160 GCUPS (all),
+	 * C2 2 300 / 2 490 / 2 500, with launches in flight 2 270 / 2 370 / 2 390 and 3 130 / 3 130 / 3 140 */
+	const long long wcap = env_ll("AT_WALK_WAVES_PER_CU", 0);
+	const long long wmain = std::max<long long>(1, wcap > 0 ? std::min<long long>((nm + 127) / 128, wcap * h->ncu) : (nm + 127) / 128);
+	HIP_TRY(h, hipMemsetAsync(h->d_queue + 8, 0, 16, r.stream));
+	const int tpw = 64 / at_walk16_team_lanes(P.g);   /* teams per wavefront */
+	const long long wteams = ((nm + 1) / 2 + tpw - 1) / tpw;
+	hipLaunchKernelGGL(wf, dim3((unsigned)((teams ? wteams : wmain) + (n_tail + 127) / 128)), dim3(64), lds, r.stream, b, bt);
+	/* (the main alignments' walker wavefronts: with fewer than one per 128 alignments, they refill from the counters) */
+	char note[128];
+	snprintf(note, sizeof note, " [walkers: %lld wavefronts%s for %lld alignments]", teams ? wteams : wmain, teams ? " of teams" : "", (long long)nm);
+	cfg_append(h, "%s", note);
+	*wnote = note;
+	HIP_TRY(h, hipGetLastError());
+	return AT_OK;
+}
+
+/* The sliver of a piece: the last n_tail pairs of b leave it and come back as the items of the sliver's layout PT (npairs = 0: no
+ * sliver) */
+static Sweep16Args split_sliver(Sweep16Args &b, int64_t n_tail, const Layout16 &PT)
+{
+	Sweep16Args bt = b;
+	bt.npairs = 0;
+	if (n_tail <= 0) return bt;
+	const int64_t nm = b.npairs - n_tail;
+	b.npairs = nm;
+	bt.npairs = n_tail;
+	bt.woff1 += nm; bt.woff2 += nm; bt.len1 += nm; bt.len2 += nm;
+	bt.score += nm;
+	if (bt.end_i) bt.end_i += nm;
+	if (bt.end_j) bt.end_j += nm;
+	if (bt.state) bt.state += nm;
+	if (bt.ops_off) bt.ops_off += nm;
+	if (bt.nops) bt.nops += nm;
+	bt.off_refb = PT.off_refb; bt.off_bound = PT.off_bound; bt.ptr_lanes = PT.ptr_lanes; bt.off_sm = PT.off_sm; bt.nsm = PT.nsm;
+	return bt;
+}
+
+static int launch_packed(at_handle *h, const BatchReq &r, int kmode, bool tb, const Packed16 &pk)
+{
+	const Layout16 &P = pk.P;
+	const int ts = pk.ts, tp_split = pk.tp_split, rag = r.rag, bits = r.bits;
+	const bool two_pass = pk.two_pass;
+	const int32_t max_len1 = r.max_len1, max_len2 = r.max_len2;
+	const int64_t npairs = r.npairs;
+	const int per_wave = 2 * (64 / P.g);
+	/* the sliver's layout (see below) */
+	const bool tail_ok = !rag && !r.only_if && P.g <= 16 && kmode != at::K_OVERLAP && env_ll("AT_TAIL_SPLIT", 1) &&
+	                     (!tp_split || P.g == 8);   /* (the walk kernels of the 8-lane groups carry their sliver's walks) */
+	Layout16 PT = P;
+	if (tail_ok) PT = layout16_for(tb && !two_pass, kmode == at::K_FITJ, max_len1, max_len2, ts, at::AT_TAIL_G, false, kmode, at::at_tail_k(P.g, P.k), two_pass ? (tp_split ? 2 : 1) : 0);
+	TpLayout tpm{}, tpt{};
+	if (two_pass) { tpm = tp_layout(P, kmode, max_len2, tp_split != 0); tpt = tp_layout(PT, kmode, max_len2, tp_split != 0); }
+	/* split two-pass: the checkpoints of a whole launch live side by side -- C2 225 KB, C3 / C4 1.1 MB per work item -- so a batch is
+	 * swept and walked in pieces whose checkpoints fit AT_CK_CAP_MB (8 192) */
+	int64_t piece = npairs;
+	int64_t brow_words = 0;
+	if (tp_split) {
+		const long long cap = env_ll("AT_CK_CAP_MB", 8192) << 20;
+		brow_words = (tpm.brow_words + 63) & ~63LL;
+		const long long tail_reserve = tail_ok ? 16LL * h->ncu * tpt.words * 4 : 0;
+		const long long items = (cap - tail_reserve - brow_words * 4) / (tpm.words * 4 + 16LL * per_wave);
+		if (items < 1) {
+			/* not even one work item's checkpoints fit the cap: this batch without the walk kernel (nothing has been launched yet) */
+			BatchReq again = r;
+			again.no_walk = " [one work item's checkpoints exceed AT_CK_CAP_MB: no separate pass 2]";
+			return align_device(h, again);
 		}
-		auto walk_lane_words = [&](const Layout16 &L) -> long long {   /* a walker lane's pointer words of one block (at_walk16.hip.h) */
-			const int cb = at::ck_steps(L.g);
-			return L.k * (cb / 4) + (kmode == at::K_FITJ ? (L.k + 3) / 4 * (cb / 4) : 0);
-		};
-		auto walk_lds = [&](const Layout16 &L, bool ptr_in_lds) -> size_t {
-			const int cb = at::ck_steps(L.g), nsm = kmode == at::K_FITJ ? L.nsm : 0;
-			return (size_t)((nsm + 1) / 2 * 2 + (L.k > 16 ? 0 : (cb + 1) * 128) + (ptr_in_lds ? 64 * walk_lane_words(L) : 0)) * 4;   /* (walk16_lds_words) */
-		};
-		std::string cfg_first, walk_last;   /* (at_last_config: the first piece's configuration, the last piece's walkers) */
-		for (int64_t first = 0; first < npairs; first += piece) {
+		piece = std::min<int64_t>(npairs, items * per_wave);
+		const long long forced = env_ll("AT_CK_PIECE_PAIRS", 0);   /* (tests: pieces of this many pairs, whatever the cap) */
+		if (forced > 0) piece = std::min<int64_t>(piece, std::max<long long>(1, forced / per_wave) * per_wave);
+	}
+	std::string cfg_first, walk_last;   /* (at_last_config: the first piece's configuration, the last piece's walkers) */
+	for (int64_t first = 0; first < npairs; first += piece) {
 		const int64_t np = std::min<int64_t>(piece, npairs - first);
 		Sweep16Args b;
 		memset(&b, 0, sizeof b);
-		b.npairs = np; b.seq = d_seq;
-		b.woff1 = (const long long *)d_woff1 + first; b.woff2 = (const long long *)d_woff2 + first;
-		b.len1 = d_len1 + first; b.len2 = d_len2 + first;
+		b.npairs = np; b.seq = r.d_seq;
+		b.woff1 = (const long long *)r.d_woff1 + first; b.woff2 = (const long long *)r.d_woff2 + first;
+		b.len1 = r.d_len1 + first; b.len2 = r.d_len2 + first;
 		b.l1 = max_len1; b.l2 = max_len2;
 		const int sc = 1 << ts;
-		b.m16 = h->m * sc; b.u16 = h->u * sc; b.o16 = h->o * sc; b.e16 = h->e * sc; b.g16 = h->j * sc; b.thresh16 = thresh16;
+		b.m16 = h->m * sc; b.u16 = h->u * sc; b.o16 = h->o * sc; b.e16 = h->e * sc; b.g16 = h->j * sc; b.thresh16 = pk.thresh16;
 		if (kmode == at::K_FITJ) {
-			int rcs = ensure_sitemask(h, max_len2, stream);
+			int rcs = ensure_sitemask(h, max_len2, r.stream);
 			if (rcs) return rcs;
 			b.sitemask = h->d_sitemask;
 		}
-		b.score = d_score + first; b.end_i = d_end_i ? d_end_i + first : nullptr; b.end_j = d_end_j ? d_end_j + first : nullptr;
-		b.state = d_state ? d_state + first : nullptr;
-		b.ops = d_ops; b.ops_off = d_ops_off ? (const long long *)d_ops_off + first : nullptr; b.nops = d_nops ? d_nops + first : nullptr;
-		b.order = rag ? d_order : nullptr;
-		b.only_if = only_if; b.only_val = only_val;
+		b.score = r.d_score + first; b.end_i = r.d_end_i ? r.d_end_i + first : nullptr; b.end_j = r.d_end_j ? r.d_end_j + first : nullptr;
+		b.state = r.d_state ? r.d_state + first : nullptr;
+		b.ops = r.d_ops; b.ops_off = r.d_ops_off ? (const long long *)r.d_ops_off + first : nullptr; b.nops = r.d_nops ? r.d_nops + first : nullptr;
+		b.order = rag ? r.d_order : nullptr;
+		b.only_if = r.only_if; b.only_val = r.only_val;
 		b.off_refb = P.off_refb; b.off_bound = P.off_bound; b.ptr_lanes = P.ptr_lanes; b.off_sm = P.off_sm; b.nsm = P.nsm;
 		Plan pl;
 		char tag16[128];
@@ -1288,7 +1557,7 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		 * main launch: +6.5 % alone, -8 % in flight -- the next batch's waves took the slots the sliver was waiting for.) */
 		/* (the sliver's items use the main items' LDS window and pointer slot: both hold either layout -- the main items' are the larger) */
 		int rc = plan_launch(h, tag16, P.k, nwork, std::max(P.off_ptr, PT.off_ptr),
-		                     tp_split ? 64 : two_pass ? std::max(tpm.words, tpt.words) : std::max(P.words - P.off_ptr, PT.words - PT.off_ptr), &pl, stream,
+		                     tp_split ? 64 : two_pass ? std::max(tpm.words, tpt.words) : std::max(P.words - P.off_ptr, PT.words - PT.off_ptr), &pl, r.stream,
 		                     [&](int st) { return (const void *)pick(st); }, P.g < 64 || rag || two_pass);
 		if (rc) return rc;
 		if (tp_split) {
@@ -1305,21 +1574,8 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			const long long sliver = nwork % pl.grid;
 			if (sliver > 0 && sliver * 4 <= pl.grid) n_tail = np - (nwork - sliver) * per_wave;   /* (four 32-lane items per 8-lane item: one per SIMD at most) */
 		}
-		Sweep16Args bt = b;
-		bt.npairs = 0;
+		Sweep16Args bt = split_sliver(b, n_tail, PT);
 		const int64_t nm = np - n_tail;
-		if (n_tail > 0) {
-			b.npairs = nm;
-			bt.npairs = n_tail;
-			bt.woff1 += nm; bt.woff2 += nm; bt.len1 += nm; bt.len2 += nm;
-			bt.score += nm;
-			if (bt.end_i) bt.end_i += nm;
-			if (bt.end_j) bt.end_j += nm;
-			if (bt.state) bt.state += nm;
-			if (bt.ops_off) bt.ops_off += nm;
-			if (bt.nops) bt.nops += nm;
-			bt.off_refb = PT.off_refb; bt.off_bound = PT.off_bound; bt.ptr_lanes = PT.ptr_lanes; bt.off_sm = PT.off_sm; bt.nsm = PT.nsm;
-		}
 		b.off_ptr = pl.off_ptr; b.ws = pl.ws; b.ws_slot_words = pl.slot_words; b.queue = h->d_queue;
 		bt.off_ptr = pl.store == 1 ? 0 : PT.off_ptr; bt.ws = pl.ws; bt.ws_slot_words = pl.slot_words; bt.queue = h->d_queue;
 		if (two_pass) {
@@ -1332,17 +1588,14 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 			const long long n_main_items = (nm + per_wave - 1) / per_wave, n_tail_items = (n_tail + 2 * (64 / at::AT_TAIL_G) - 1) / (2 * (64 / at::AT_TAIL_G));
 			const long long end_words = ((np * 4) + 63) & ~63LL;
 			const size_t need = (size_t)(brow_words + end_words + n_main_items * tpm.words + n_tail_items * tpt.words) * 4;
-			void *pc = h->d_ck; size_t have = h->ck_bytes;
 			const std::string err_before = h->err, g_err_before = g_err;
-			rc = grow(h, &pc, &have, need, "ck");
-			h->d_ck = (uint32_t *)pc; h->ck_bytes = have;
+			rc = grow_words(h, &h->d_ck, &h->ck_bytes, need, "ck");
 			if (rc && first == 0) {
 				/* no room for a launch's checkpoints (several handles on one card, a small AT_CK_CAP_MB would have cut the batch into pieces):
 				 * nothing has been launched yet -- the same batch with the rounds inside the sweep's kernel, whose checkpoints live in the
 				 * resident wavefronts' slots.  A fallback that works is no error: the hipMalloc text goes again */
 				h->ck_alloc_failed = true;
-				rc = align_device(h, mode, npairs, d_seq, bits, d_woff1, d_len1, d_woff2, d_len2, max_len1, max_len2, uniform_shape, want_traceback,
-				                  d_score, d_end_i, d_end_j, d_state, d_ops, d_ops_off, d_nops, stream_, ap_n, ap_first, d_order, rag, only_if, only_val);
+				rc = align_device(h, r);
 				if (rc == AT_OK) {
 					snprintf(h->err, sizeof h->err, "%s", err_before.c_str());
 					snprintf(g_err, sizeof g_err, "%s", g_err_before.c_str());
@@ -1359,207 +1612,66 @@ static int align_device(at_handle *h, int mode, int64_t npairs,
 		if (!fn16 || (P.g != 64 && pl.store == 2)) return fail(h, AT_ERR_RANGE, "no packed kernel for this shape (rows/lane=%d, store=%d)", P.k, pl.store);
 		if (pl.dyn_lds > 48 * 1024)
 			HIP_TRY(h, hipFuncSetAttribute((const void *)fn16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.dyn_lds));
-		hipLaunchKernelGGL(fn16, dim3((unsigned)pl.grid), dim3(64), pl.dyn_lds, stream, b, bt);
+		hipLaunchKernelGGL(fn16, dim3((unsigned)pl.grid), dim3(64), pl.dyn_lds, r.stream, b, bt);
 		HIP_TRY(h, hipGetLastError());
-		if (tp_split && !(AT_DIAG_SWEEP_ONLY && env_ll("AT_DIAG_NO_WALK_KERNEL", 0))) {   /* (diagnostic builds, -DAT_DIAG_SWEEP_ONLY=1: AT_DIAG_NO_WALK_KERNEL=1
-			* -- throw-away runs without pass 2: what does the sweep alone reach?  Every pair reports garbage ops.  The product ignores the knob) */
-			/* the 64-lane groups: teams of lanes per pair of alignments (walk16_team_wave; AT_WALK_TEAMS=0: one walker per half-lane there too) */
-			const bool teams = env_ll("AT_WALK_TEAMS", P.g == 64 ? 1 : 0) && at_pick_walk16(kmode, P.g, P.k, ts, bits, 1);
-			at_walk16_fn wf = at_pick_walk16(kmode, P.g, P.k, ts, bits, teams);
-			if (!wf) return fail(h, AT_ERR_RANGE, "no walk kernel for %d-lane groups x %d rows", P.g, P.k);
-			const size_t lds = std::max(walk_lds(P, true), tail_ok ? walk_lds(PT, true) : 0);
-			if (lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute((const void *)wf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-			/* the main units' walkers: one wavefront per 128 alignments (LDS admits four per CU; the others queue).  AT_WALK_WAVES_PER_CU = n:
-			 * at most n per CU, persistent, which refill their halves from the counters behind the sweep's work counter -- fewer
-			 * wavefront-rounds, but a chain of them per wavefront: C4 one launch at a time 1 450 (n = 1) / 1 820 (2) / 2 160 GCUPS (all),
-			 * C2 2 300 / 2 490 / 2 500, with launches in flight 2 270 / 2 370 / 2 390 and 3 130 / 3 130 / 3 140 */
-			const long long wcap = env_ll("AT_WALK_WAVES_PER_CU", 0);
-			const long long wmain = std::max<long long>(1, wcap > 0 ? std::min<long long>((nm + 127) / 128, wcap * h->ncu) : (nm + 127) / 128);
-			HIP_TRY(h, hipMemsetAsync(h->d_queue + 8, 0, 16, stream));
-			const int tpw = 64 / at_walk16_team_lanes(P.g);   /* teams per wavefront */
-			const long long wteams = ((nm + 1) / 2 + tpw - 1) / tpw;
-			hipLaunchKernelGGL(wf, dim3((unsigned)((teams ? wteams : wmain) + (n_tail + 127) / 128)), dim3(64), lds, stream, b, bt);
-			/* (the main alignments' walker wavefronts: with fewer than one per 128 alignments, they refill from the counters) */
-			char wnote[128];
-			snprintf(wnote, sizeof wnote, " [walkers: %lld wavefronts%s for %lld alignments]", teams ? wteams : wmain, teams ? " of teams" : "", (long long)nm);
-			cfg_append(h, "%s", wnote);
-			walk_last = wnote;
-			HIP_TRY(h, hipGetLastError());
+		/* (diagnostic builds, -DAT_DIAG_SWEEP_ONLY=1: AT_DIAG_NO_WALK_KERNEL=1 -- throw-away runs without pass 2: what does the sweep alone
+		 * reach?  Every pair reports garbage ops.  The product ignores the knob) */
+		if (tp_split && !(AT_DIAG_SWEEP_ONLY && env_ll("AT_DIAG_NO_WALK_KERNEL", 0))) {
+			rc = launch_walk16(h, r, kmode, pk, PT, tail_ok, b, bt, &walk_last);
+			if (rc) return rc;
 		}
 		if (n_tail > 0)
 			cfg_append(h, " + last %lld pairs as 32-lane items (rows/lane=%d)", (long long)n_tail, PT.k);
 		if (first == 0) cfg_first = h->cfg;
-		}
-		if (piece < npairs) snprintf(h->cfg, sizeof h->cfg, "%.360s; in pieces of %lld pairs%s%s", cfg_first.c_str(), (long long)piece,
-		                              walk_last.empty() ? "" : "; last piece", walk_last.c_str());
-		if (ck_note[0]) cfg_append(h, "%s", ck_note);
-		return AT_OK;
 	}
-
-	/* ---- edit alignments (at_set_edit_traceback): the bit-parallel fill keeps its columns, the same wavefront walks them
-	 * (at_edit_tb.hip.h).  Outside the domain the call fails: no silent fall back to the number alone ---- */
-	if (edit_tb) {
-		const size_t lds = at::myers_window_bytes(64, max_len2);   /* the 64 s2 windows of a wavefront */
-		if (h->u != 1) return fail(h, AT_ERR_DOMAIN, "edit alignments need the unit mismatch cost: u = %d, not 1", h->u);
-		if (bits != 2) return fail(h, AT_ERR_DOMAIN, "edit alignments need a 2-bit batch: some base is not one of ACGT");
-		if (max_len1 > 1024) return fail(h, AT_ERR_DOMAIN, "edit alignments: max_len1 = %d exceeds 1024", max_len1);
-		if (lds > 60 * 1024) return fail(h, AT_ERR_DOMAIN, "edit alignments: max_len2 = %d exceeds 3792 (64 windows of packed words in 60 KB of LDS)", max_len2);
-		const int w = at::class_rows(at::kMyersLaneWords, max_len1);
-		at_edit_tb_fn fn = at_pick_edit_tb(w);
-		if (!fn) return fail(h, AT_ERR_ARG, "no edit alignment kernel for %d words per lane", w);
-		/* the slab: one column is W words x 2 planes x 64 lanes; bounded like the pointer slots of plan_launch */
-		const long long slab_words = (long long)std::max(max_len2, 1) * w * 128;
-		const long long cap = env_ll("AT_WS_CAP_MB", 16384) << 20;
-		if (slab_words * 4 > cap)
-			return fail(h, AT_ERR_NOMEM, "edit alignments: one work item needs %lld workspace bytes (cap %lld)", slab_words * 4, cap);
-		int occ = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, 64, lds) != hipSuccess || occ <= 0) occ = 8;
-		const long long per_cu = std::max(1LL, std::min<long long>(occ, env_ll("AT_WAVES_PER_CU", 16)));
-		const long long grid = std::max(1LL, std::min<long long>(std::min<long long>((npairs + 63) / 64, per_cu * h->ncu), cap / (slab_words * 4)));
-		{
-			void *p = h->d_ws; size_t have = h->ws_bytes;
-			int rc = grow(h, &p, &have, (size_t)(grid * slab_words * 4), "ws");
-			h->d_ws = (uint32_t *)p; h->ws_bytes = have;
-			if (rc) return rc;
-		}
-		at::EditTbArgs ea;
-		memset(&ea, 0, sizeof ea);
-		ea.m.npairs = npairs; ea.m.seq = d_seq;
-		ea.m.woff1 = (const long long *)d_woff1; ea.m.woff2 = (const long long *)d_woff2; ea.m.len1 = d_len1; ea.m.len2 = d_len2;
-		ea.m.max_l1 = max_len1; ea.m.max_l2 = max_len2;
-		ea.m.score = d_score; ea.m.end_i = d_end_i; ea.m.end_j = d_end_j; ea.m.state = d_state; ea.m.nops = d_nops;
-		ea.m.order = d_order;
-		ea.ops = d_ops; ea.ops_off = (const long long *)d_ops_off;
-		ea.slab = h->d_ws; ea.slab_words = slab_words;
-		if (int rcq = ensure_queue(h, stream)) return rcq;
-		ea.m.queue = h->d_queue;
-		hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, stream, ea);
-		HIP_TRY(h, hipGetLastError());
-		snprintf(h->cfg, sizeof h->cfg, "myers-tb bits=2 words/lane=%d (64 pairs/wave) lds=%zuB slab=%lldB waves/cu<=%lld grid=%lld", w, lds,
-		         slab_words * 4, per_cu, grid);
-		return AT_OK;
-	}
-
-	/* ---- edit distance with unit mismatch cost: bit-parallel kernel (at_myers.hip.h), any mix of lengths ---- */
-	/* (bytes of LDS for the s2 windows of the n alignments of a wavefront; two must fit, or the cell-by-cell kernel takes the batch) */
-	auto myers_windows = [&](int n) { return at::myers_window_bytes(n, max_len2); };
-	if (kmode == at::K_EDIT && h->u == 1 && bits == 2 && max_len1 <= 32768 && myers_windows(2) <= 60 * 1024 && env_ll("AT_MYERS", 1)) {
-		/* lanes per alignment and words per lane: reads of up to AT_MYERS_LANE_MAX (1 024) bases one alignment per LANE -- 5, 8, 16 or 32
-		 * words, 64 s2 windows in LDS (second sequences of up to ~3 500 bases) -- else 32 lanes; the 16- and 32-word forms only for batches
-		 * of AT_MYERS_LANE_MIN_PAIRS (16 384: one wavefront per CU) and more -- 10 000 pairs of 1 000 x 1 000 are 157 wavefronts on 1 024
-		 * SIMDs, 19 TCUPS against 31 on 32-lane groups; 131 072 of them 43 against 36.  AT_MYERS_GROUP = 8: the round-2 form, eight lanes
-		 * for reads of up to 256 bases and 32 beyond (A/B) */
-		const long long lane_max = env_ll("AT_MYERS_LANE_MAX", 1024);
-		const bool per_lane = max_len1 <= lane_max && max_len1 <= 1024 && myers_windows(64) <= 60 * 1024 &&
-		                      (max_len1 <= 256 || npairs >= env_ll("AT_MYERS_LANE_MIN_PAIRS", 16384)) && env_ll("AT_MYERS_GROUP", 1) == 1;
-		const int g = per_lane ? 1 : max_len1 <= 256 && myers_windows(8) <= 60 * 1024 ? 8 : 32;
-		const int w = per_lane ? at::class_rows(at::kMyersLaneWords, max_len1) : at::class_rows(at::kMyersGroupWords, max_len1);
-		at_myers_fn fn = at_pick_myers(w, g);
-		const int per_wave = 64 / g;
-		at::MyersArgs m;
-		memset(&m, 0, sizeof m);
-		m.npairs = npairs; m.seq = d_seq;
-		m.woff1 = (const long long *)d_woff1; m.woff2 = (const long long *)d_woff2; m.len1 = d_len1; m.len2 = d_len2;
-		m.max_l1 = max_len1; m.max_l2 = max_len2;
-		m.score = d_score; m.end_i = d_end_i; m.end_j = d_end_j; m.state = d_state; m.nops = d_nops;
-		m.order = d_order;
-		m.ap_n = ap_n; m.ap_first = ap_first;
-		if (int rcq = ensure_queue(h, stream)) return rcq;
-		m.queue = h->d_queue;
-		const size_t lds = myers_windows(per_wave);
-		if (lds > 60 * 1024) return fail(h, AT_ERR_RANGE, "second sequence too long for the bit-parallel kernel's LDS window");
-		int occ = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, 64, lds) != hipSuccess || occ <= 0) occ = 8;
-		const long long grid = std::max(1LL, std::min<long long>((npairs + per_wave - 1) / per_wave, (long long)occ * h->ncu));
-		hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(64), lds, stream, m);
-		HIP_TRY(h, hipGetLastError());
-		snprintf(h->cfg, sizeof h->cfg, "myers bits=2 words/lane=%d %dx%d-lane groups (%d pairs/wave) lds=%zuB waves/cu<=%d grid=%lld", w, per_wave, g, per_wave,
-		         lds, occ, grid);
-		return AT_OK;
-	}
-
-	/* ---- all-vs-all overlap scores with a threshold (at_set_min_score): the bit-parallel filter (at_myers.hip.h, SEMI) bounds every
-	 * pair's score from above at a seventh of the sweep's cost; only pairs whose bound reaches the threshold are swept.  The filter
-	 * leaves (upper bound, state 0) in every pair's result slot and the candidates' indices in a list; the sweep below takes the
-	 * list and its length from the device and overwrites the candidates' slots with exact results.  No host round trip. ---- */
-	const int *npairs_dev = nullptr;
-	char filter_note[96] = "";
-	if (kmode == at::K_OVERLAP && !tb && ap_n > 0 && h->min_on && !d_order && !only_if && bits == 2 && max_len1 >= 1 && max_len1 <= 1024 &&
-	    npairs < (1LL << 31) - 64 && env_ll("AT_OVERLAP_FILTER", 1)) {
-		/* 2 score <= 2 m b - (2 c - m) D', c = min(m - u, m / 2 - o): needs m >= 0 and 2 c > m */
-		const long long k2 = std::min<long long>(2LL * (h->m - h->u), (long long)h->m - 2LL * h->o) - h->m;
-		const int w = at::class_rows(at::kMyersLaneWords, max_len1);
-		at_myers_fn ffn = at_pick_myers_semi(w);
-		if (h->m >= 0 && k2 > 0 && k2 < 4096 && h->m < 4096 && myers_windows(64) <= 60 * 1024 && ffn) {
-			int rc = grow(h, &h->d_order, &h->order_bytes, ((size_t)npairs + 64) * 4);
-			if (rc) return rc;
-			int *cand = (int *)h->d_order, *count = cand + ((npairs + 15) & ~15LL);
-			HIP_TRY(h, hipMemsetAsync(count, 0, 4, stream));
-			at::MyersArgs m;
-			memset(&m, 0, sizeof m);
-			m.npairs = npairs; m.seq = d_seq;
-			m.woff1 = (const long long *)d_woff1; m.woff2 = (const long long *)d_woff2; m.len1 = d_len1; m.len2 = d_len2;
-			m.max_l1 = max_len1; m.max_l2 = max_len2;
-			m.score = d_score; m.end_i = d_end_i; m.end_j = d_end_j; m.state = d_state;
-			m.ap_n = ap_n; m.ap_first = ap_first;
-			m.semi_m2 = 2 * h->m; m.semi_k = (int)k2; m.semi_min2 = (int)std::max<long long>(std::min<long long>(2LL * h->min_score, INT32_MAX), INT32_MIN);
-			m.cand_order = cand; m.cand_count = count;
-			if (int rcq = ensure_queue(h, stream)) return rcq;
-			m.queue = h->d_queue;
-			const size_t lds = myers_windows(64);
-			int occ = 0;
-			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)ffn, 64, lds) != hipSuccess || occ <= 0) occ = 8;
-			const long long fgrid = std::max(1LL, std::min<long long>((npairs + 63) / 64, (long long)occ * h->ncu));
-			hipLaunchKernelGGL(ffn, dim3((unsigned)fgrid), dim3(64), lds, stream, m);
-			HIP_TRY(h, hipGetLastError());
-			d_order = cand; npairs_dev = count;
-			snprintf(filter_note, sizeof filter_note, "overlap filter (bit-parallel bound, %d words/lane, min score %d) + ", w, h->min_score);
-		}
-	}
-
-	/* the int32 kernels read 2-bit scores from a byte LUT (the packed ones above from a 16-bit one) */
-	if (bits == 2 && !scores_fit_byte(h, mode))
-		return fail(h, AT_ERR_RANGE, "the int32 2-bit kernels need |16*score| <= 127 (m=%d u=%d o=%d): pack the batch with bits=8", h->m, h->u, h->o);
-	const Layout L = layout_for(kmode, bits, tb, max_len1, max_len2);
-	if (L.words >= (1LL << 30)) return fail(h, AT_ERR_RANGE, "pair too large: %lld workspace words", L.words);
-	SweepArgs a;
-	memset(&a, 0, sizeof a);
-	a.npairs = npairs;
-	a.seq = d_seq;
-	a.woff1 = (const long long *)d_woff1; a.len1 = d_len1;
-	a.woff2 = (const long long *)d_woff2; a.len2 = d_len2;
-	a.m16 = h->m * 16; a.u16 = h->u * 16; a.o16 = h->o * 16; a.e16 = h->e * 16; a.g16 = h->j * 16;
-	a.u_raw = h->u;
-	a.score = d_score; a.end_i = d_end_i; a.end_j = d_end_j; a.state = d_state;
-	a.ops = d_ops; a.ops_off = (const long long *)d_ops_off; a.nops = d_nops;
-	a.off_bound = L.off_bound; a.ptr_lanes = L.ptr_lanes; a.off_sm = L.off_sm; a.nsm = L.nsm;
-	a.ap_n = ap_n; a.ap_first = ap_first; a.order = d_order;
-	a.only_if = only_if; a.only_val = only_val;
-	a.npairs_dev = npairs_dev;
-	if (kmode == at::K_FITJ) {
-		int rc = ensure_sitemask(h, max_len2, stream);
-		if (rc) return rc;
-		a.sitemask = h->d_sitemask;
-	}
-	Plan pl;
-	char tag[32];
-	snprintf(tag, sizeof tag, "int32 bits=%d", bits);
-	int rc = plan_launch(h, tag, L.k, npairs, L.off_ptr, L.words - L.off_ptr, &pl, stream, [&](int st) {
-		return (const void *)(bits == 2 ? at_pick32_b2(kmode, L.k, st, tb) : at_pick32_b8(kmode, L.k, st, tb));
-	});
-	if (rc) return rc;
-	a.off_ptr = pl.off_ptr; a.ws = pl.ws; a.ws_slot_words = pl.slot_words; a.queue = h->d_queue;
-	a.max_l1 = max_len1; a.max_l2 = max_len2;
-	at_sweep_fn fn = bits == 2 ? at_pick32_b2(kmode, L.k, pl.store, tb) : at_pick32_b8(kmode, L.k, pl.store, tb);
-	if (pl.dyn_lds > 48 * 1024)
-		HIP_TRY(h, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.dyn_lds));
-	hipLaunchKernelGGL(fn, dim3((unsigned)pl.grid), dim3(64), pl.dyn_lds, stream, a);
-	HIP_TRY(h, hipGetLastError());
-	if (filter_note[0]) {
-		const std::string tail = h->cfg;
-		snprintf(h->cfg, sizeof h->cfg, "%s%.200s", filter_note, tail.c_str());
-	}
+	if (piece < npairs) snprintf(h->cfg, sizeof h->cfg, "%.360s; in pieces of %lld pairs%s%s", cfg_first.c_str(), (long long)piece,
+	                              walk_last.empty() ? "" : "; last piece", walk_last.c_str());
+	if (pk.ck_note[0]) cfg_append(h, "%s", pk.ck_note);
 	return AT_OK;
+}
+
+/* The routing order.  A rung that takes the batch returns; the two fallbacks of the packed path come back in here with the same
+ * request (the cap fallback with no_walk set, before anything was queued; the allocation fallback with ck_alloc_failed set, after
+ * plan_launch and the site mask's upload of the first piece, before any launch) */
+static int align_device(at_handle *h, const BatchReq &r)
+{
+	if (!h) return fail(nullptr, AT_ERR_ARG, "at_align_batch_device: NULL handle");
+	if (r.mode < AT_MODE_GLOBAL || r.mode > AT_MODE_EDIT) return fail(h, AT_ERR_ARG, "unknown mode %d", r.mode);
+	if (r.npairs < 0 || r.max_len1 < 0 || r.max_len2 < 0) return fail(h, AT_ERR_ARG, "negative size");
+	if (r.bits != 2 && r.bits != 8) return fail(h, AT_ERR_ARG, "bits must be 2 or 8");
+	if (r.npairs == 0) return AT_OK;
+	if (!r.d_seq || !r.d_woff1 || !r.d_len1 || !r.d_woff2 || !r.d_len2 || !r.d_score) return fail(h, AT_ERR_ARG, "NULL device pointer");
+	/* edit alignments (at_set_edit_traceback): batches only -- the all-pairs entries keep the number */
+	const bool edit_tb = r.want_traceback && r.mode == AT_MODE_EDIT && r.edit_tb && r.ap_n == 0;
+	const bool tb = r.want_traceback && r.mode != AT_MODE_EDIT;
+	if ((tb || edit_tb) && (!r.d_ops || !r.d_ops_off || !r.d_nops)) return fail(h, AT_ERR_ARG, "traceback wanted but ops buffers are NULL");
+	HIP_TRY(h, hipSetDevice(h->device));
+	drop_stale_error();
+
+	/* exact-int32 range: real scores stay within 2^24, sentinel at -2^26 (at_sweep.hip.h) */
+	long long maxabs = 0;
+	for (int v : {h->m, h->u, h->o, h->e, h->j}) maxabs = std::max<long long>(maxabs, std::llabs((long long)v));
+	maxabs = std::max<long long>(maxabs, 1);
+	if (maxabs * ((long long)r.max_len1 + r.max_len2 + 2) >= (1LL << 24))
+		return fail(h, AT_ERR_RANGE, "scores may exceed the exact range: max|param|=%lld, l1+l2=%lld", maxabs,
+		            (long long)r.max_len1 + r.max_len2);
+
+	h->last_span = r.max_len1 + r.max_len2;
+	const int kmode = r.mode == AT_MODE_GLOBAL ? at::K_GLOBAL : r.mode == AT_MODE_LOCAL ? at::K_LOCAL
+	                : r.mode == AT_MODE_FIT ? (h->use_jump ? at::K_FITJ : at::K_FIT)
+	                : r.mode == AT_MODE_OVERLAP ? at::K_OVERLAP : at::K_EDIT;
+
+	if (r.mode == AT_MODE_EDIT && r.edit_infix) return launch_infix(h, r);
+	if (auto_uniform_applies(h, r, kmode)) return launch_auto_uniform(h, r);
+	Packed16 pk;
+	if (int rc = route_packed(h, r, kmode, tb, &pk)) return rc;
+	if (pk.ts) return launch_packed(h, r, kmode, tb, pk);
+	if (edit_tb) return launch_edit_tb(h, r);
+	if (myers_takes(h, r, kmode)) return launch_myers(h, r);
+	const int *order = r.d_order, *npairs_dev = nullptr;
+	char filter_note[96] = "";
+	if (int rc = overlap_filter(h, r, kmode, tb, &order, &npairs_dev, filter_note)) return rc;
+	return launch_int32(h, r, kmode, tb, order, npairs_dev, filter_note);
 }
 
 /* ---- host entry: 2-bit packing while staging (round 4) ----
@@ -1824,6 +1936,16 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 	 * pairs and the launches are at_ragplan.h's; everything else runs on the int32 kernel, pairs handed out largest first. */
 	int *d_order = nullptr;
 	bool frames = false;
+	/* a launch over this chunk's descriptors and results: n pairs of at most m1 x m2 */
+	auto chunk_req = [&](int64_t n, int32_t m1, int32_t m2) {
+		BatchReq q(h);
+		q.mode = mode; q.npairs = n; q.d_seq = d_words; q.bits = bits; q.stream = s;
+		q.d_woff1 = d_woff1; q.d_len1 = d_len1; q.d_woff2 = d_woff2; q.d_len2 = d_len2; q.max_len1 = m1; q.max_len2 = m2;
+		q.want_traceback = tb ? 1 : 0;
+		q.d_score = d_score; q.d_end_i = d_ei; q.d_end_j = d_ej; q.d_state = d_st;
+		if (tb) { q.d_ops = d_ops; q.d_ops_off = d_opsoff; q.d_nops = d_nops; }
+		return q;
+	};
 	const bool ragged = !uniform && npairs > 1 && npairs < (1LL << 31);
 	if (!ragged) {
 		rc = settle_alphabet();
@@ -1876,16 +1998,17 @@ static int align_host(at_handle *h, int mode, int64_t npairs, const uint8_t *seq
 		d_order = (int *)h->d_order;
 		HIP_TRY(h, hipMemcpyAsync(d_order, h->hp_order, order.size() * 4, hipMemcpyHostToDevice, s));
 		for (const at::RagLaunch &L : plan.launches) {
-			rc = align_device(h, mode, L.b1 - L.b0, d_words, bits, d_woff1, d_len1, d_woff2, d_len2, L.f1, L.f2, 0, tb ? 1 : 0,
-			                  d_score, d_ei, d_ej, d_st, tb ? d_ops : nullptr, tb ? d_opsoff : nullptr, tb ? d_nops : nullptr, s,
-			                  0, 0, d_order + L.b0, L.g);
+			BatchReq fr = chunk_req(L.b1 - L.b0, L.f1, L.f2);
+			fr.d_order = d_order + L.b0; fr.rag = L.g;
+			rc = align_device(h, fr);
 			if (rc) return rc;
 		}
 		if (frames) cfg_append(h, mode == AT_MODE_LOCAL ? " (%d frames)" : " (%d frames, equal-l1 work items)", (int)plan.launches.size());
 	}
 	if (!frames) {
-		rc = align_device(h, mode, npairs, d_words, bits, d_woff1, d_len1, d_woff2, d_len2, max1, max2, uniform ? 1 : 0, tb ? 1 : 0,
-		                  d_score, d_ei, d_ej, d_st, tb ? d_ops : nullptr, tb ? d_opsoff : nullptr, tb ? d_nops : nullptr, s, 0, 0, d_order);
+		BatchReq br = chunk_req(npairs, max1, max2);
+		br.uniform_shape = uniform ? 1 : 0; br.d_order = d_order;
+		rc = align_device(h, br);
 		if (rc) return rc;
 	}
 	htrace("chunk: sweep queued, pair", pair_base);
@@ -2141,6 +2264,16 @@ struct ReadSet {
 	int bits = 2, maxlen = 0;
 };
 
+/* pairs [first, first + n) of the triangle over the nreads reads of a set */
+static BatchReq triangle_req(const at_handle *h, int mode, const ReadSet &rs, int64_t nreads, int64_t first, int64_t n, hipStream_t s)
+{
+	BatchReq r(h);
+	r.mode = mode; r.npairs = n; r.d_seq = rs.d_words; r.bits = rs.bits; r.stream = s;
+	r.d_woff1 = r.d_woff2 = rs.d_swoff; r.d_len1 = r.d_len2 = rs.d_len; r.max_len1 = r.max_len2 = rs.maxlen;
+	r.ap_n = nreads; r.ap_first = first;
+	return r;
+}
+
 /* hands out 256-byte-aligned typed sub-ranges of one buffer.  A function says its layout ONCE, as a function of a Carver, and carve()
  * runs it twice: without a base, where take() only counts -- the bytes asked of grow() -- and then on the buffer */
 struct Carver {
@@ -2288,8 +2421,9 @@ static int allpairs_scores(at_handle *h, int mode, int64_t nreads, const ReadSet
 		const int q = (int)(c & 1);
 		const int64_t lo = c * chunk, n = std::min(chunk, npairs - lo);
 		/* (slice c - 2, the last user of buffer set q, was delivered before slice c - 1 was queued) */
-		rc = align_device(h, mode, n, rs.d_words, rs.bits, rs.d_swoff, rs.d_len, rs.d_swoff, rs.d_len, rs.maxlen, rs.maxlen, 0, 0,
-		                  dres(q, 0), dres(q, 1), dres(q, 2), dres(q, 3), nullptr, nullptr, nullptr, s, nreads, first_pair + lo);
+		BatchReq r = triangle_req(h, mode, rs, nreads, first_pair + lo, n, s);
+		r.d_score = dres(q, 0); r.d_end_i = dres(q, 1); r.d_end_j = dres(q, 2); r.d_state = dres(q, 3);
+		rc = align_device(h, r);
 		if (rc) { (void)hipDeviceSynchronize(); return rc; }
 		if (c == 0) cfg0 = h->cfg;
 		HIP_TRY(h, hipEventRecord(h->ev_sweep[q], s));
@@ -2520,8 +2654,12 @@ static int search_lists(at_handle *h, int mode, const QuerySets &qt, const ReadS
 			da.qperm = d_qperm; da.tperm = d_tperm; da.swoff = (const long long *)rs.d_swoff; da.slen = rs.d_len;
 			da.woff1 = (long long *)d_woff1; da.woff2 = (long long *)d_woff2; da.len1 = d_len1; da.len2 = d_len2;
 			HIP_TRY(h, at_search_desc_launch(&da, h->ncu, s));
-			rc = align_device(h, mode, n, rs.d_words, rs.bits, d_woff1, d_len1, d_woff2, d_len2, B.l1, B.l2, B.uniform ? 1 : 0, 0,
-			                  d_r[0], d_r[1], d_r[2], d_r[3], nullptr, nullptr, nullptr, s, 0, 0);
+			BatchReq r(h);
+			r.mode = mode; r.npairs = n; r.d_seq = rs.d_words; r.bits = rs.bits; r.stream = s;
+			r.d_woff1 = d_woff1; r.d_len1 = d_len1; r.d_woff2 = d_woff2; r.d_len2 = d_len2; r.max_len1 = B.l1; r.max_len2 = B.l2;
+			r.uniform_shape = B.uniform ? 1 : 0;
+			r.d_score = d_r[0]; r.d_end_i = d_r[1]; r.d_end_j = d_r[2]; r.d_state = d_r[3];
+			rc = align_device(h, r);
 			if (rc) { (void)hipStreamSynchronize(s); return rc; }
 			if (nslices == 0) cfg0 = h->cfg;
 			rc = merge_slice(h, qo, lb, d_qperm, d_tperm, d_r, s0, n, B.ntb, B.qa, B.ta, k, mode == AT_MODE_EDIT, use_cutoff, cutoff);
@@ -2702,6 +2840,18 @@ struct WindowBufs {
 	int32_t *len1, *len2, *aux, *sc, *ei, *ej, *st, *nops, *ncigar, *ncout, *stats;   /* aux: the windows' starts, or the pairs' slot sizes */
 };
 
+/* the traceback pass over n windows: their descriptors, results and op slots */
+static BatchReq window_req(const at_handle *h, int mode, int64_t n, const ReadSet &rs, const WindowBufs &w, int32_t max1, int32_t max2, hipStream_t s)
+{
+	BatchReq r(h);
+	r.mode = mode; r.npairs = n; r.d_seq = rs.d_words; r.bits = rs.bits; r.stream = s;
+	r.d_woff1 = w.woff1; r.d_len1 = w.len1; r.d_woff2 = w.woff2; r.d_len2 = w.len2; r.max_len1 = max1; r.max_len2 = max2;
+	r.want_traceback = 1;
+	r.d_score = w.sc; r.d_end_i = w.ei; r.d_end_j = w.ej; r.d_state = w.st;
+	r.d_ops = w.ops; r.d_ops_off = w.ops_off; r.d_nops = w.nops;
+	return r;
+}
+
 static int window_carve(at_handle *h, int64_t n, int64_t dcap, size_t front_bytes, bool eidx, bool ncout, void **ops_buf, size_t *ops_have, size_t ops_need,
                         WindowBufs &w)
 {
@@ -2783,14 +2933,11 @@ static int scan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadS
 	wa.w_score = w.sc; wa.w_end_j = w.ej; wa.ncigar = w.ncigar; wa.stats = w.stats; wa.ncigar_out = w.ncout; wa.bad = w.bad;
 	HIP_TRY(h, at_scan_window_launch(&wa, h->ncu, s));
 	const std::string cfg0 = h->cfg;
-	{
-		/* the window pass is an infix batch with op lists whatever the handle's settings say; they are put back at once */
-		const int keep_infix = h->edit_infix, keep_tb = h->edit_tb;
-		h->edit_infix = 1; h->edit_tb = 1; h->infix_anchor = anchor;
-		rc = align_device(h, AT_MODE_EDIT, n, rs.d_words, 2, w.woff1, w.len1, w.woff2, w.len2, maxq, max2, 0, 1, w.sc, w.ei, w.ej, w.st,
-		                  w.ops, w.ops_off, w.nops, s, 0, 0);
-		h->edit_infix = keep_infix; h->edit_tb = keep_tb; h->infix_anchor = 0;
-	}
+	/* the window pass is an infix batch with op lists whatever the handle's settings say */
+	BatchReq r = window_req(h, AT_MODE_EDIT, n, rs, w, maxq, max2, s);
+	r.bits = 2;
+	r.edit_infix = 1; r.edit_tb = 1; r.infix_anchor = anchor;
+	rc = align_device(h, r);
 	if (rc) { (void)hipStreamSynchronize(s); return rc; }
 	const std::string cfg1 = h->cfg;
 	rc = at_cigar_batch_device(h, n, rs.d_words, 2, w.woff1, w.woff2, w.ei, w.ej, w.ops, w.ops_off, w.nops, flags, w.ncigar, w.stats, w.coff, w.cigar, dcap, s);
@@ -2964,8 +3111,13 @@ static int localscan_lists(at_handle *h, const QuerySets &qt, const ReadSet &rs,
 				for (long long y = ya; y < yb; y += chunk) {
 					sa.y0 = y; sa.nitems = std::min<long long>(chunk, yb - y);
 					HIP_TRY(h, at_localscan_desc_launch(&sa, h->ncu, s));
-					rc = align_device(h, AT_MODE_LOCAL, sa.nitems, rs.d_words, rs.bits, d_woff1, d_len1, d_woff2, d_len2, B.l1,
-					                  pass ? rag_most : (int32_t)(tile + ov), pass ? 0 : 1, 0, d_r[0], d_r[1], d_r[2], d_r[3], nullptr, nullptr, nullptr, s, 0, 0);
+					BatchReq r(h);
+					r.mode = AT_MODE_LOCAL; r.npairs = sa.nitems; r.d_seq = rs.d_words; r.bits = rs.bits; r.stream = s;
+					r.d_woff1 = d_woff1; r.d_len1 = d_len1; r.d_woff2 = d_woff2; r.d_len2 = d_len2;
+					r.max_len1 = B.l1; r.max_len2 = pass ? rag_most : (int32_t)(tile + ov);
+					r.uniform_shape = pass ? 0 : 1;
+					r.d_score = d_r[0]; r.d_end_i = d_r[1]; r.d_end_j = d_r[2]; r.d_state = d_r[3];
+					rc = align_device(h, r);
 					if (rc) { (void)hipStreamSynchronize(s); return rc; }
 					if (nslices == 0) cfg0 = h->cfg;
 					HIP_TRY(h, at_localscan_fold_launch(&sa, h->ncu, s));
@@ -3040,8 +3192,7 @@ static int localscan_cigars(at_handle *h, int64_t nq, int k, int strands, const 
 		wa.woff1 = (long long *)w.woff1; wa.woff2 = (long long *)w.woff2; wa.len1 = w.len1; wa.len2 = w.len2; wa.ws = w.aux;
 		wa.w_score = w.sc; wa.w_end_i = w.ei; wa.w_end_j = w.ej; wa.ncigar = w.ncigar; wa.stats = w.stats; wa.bad = w.bad;
 		HIP_TRY(h, at_localscan_window_launch(&wa, h->ncu, s));
-		rc = align_device(h, AT_MODE_LOCAL, n, rs.d_words, rs.bits, w.woff1, w.len1, w.woff2, w.len2, maxq, max2, 0, 1, w.sc, w.ei, w.ej, w.st,
-		                  w.ops, w.ops_off, w.nops, s, 0, 0);
+		rc = align_device(h, window_req(h, AT_MODE_LOCAL, n, rs, w, maxq, max2, s));
 		if (rc) { (void)hipStreamSynchronize(s); return rc; }
 		if (cfg1.empty()) cfg1 = h->cfg;
 		rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, w.woff1, w.woff2, w.ei, w.ej, w.ops, w.ops_off, w.nops, flags, w.ncigar, w.stats, w.coff, w.cigar, dcap, s);
@@ -3409,8 +3560,11 @@ static int allpairs_tb_slice(at_handle *h, int mode, int64_t nreads, const ReadS
 	int32_t *d_st = (int32_t *)(dout + 3 * b_res), *d_nops = (int32_t *)(dout + 4 * b_res);
 	uint8_t *d_ops = (uint8_t *)(dout + 5 * b_res);
 	int64_t *d_poff = (int64_t *)(dout + 5 * b_res + b_ops);
-	rc = align_device(h, mode, npairs, rs.d_words, rs.bits, rs.d_swoff, rs.d_len, rs.d_swoff, rs.d_len, maxlen, maxlen, 0, 1, d_score, d_ei, d_ej, d_st,
-	                  d_ops, d_opsoff, d_nops, s, nreads, first_pair);
+	BatchReq r = triangle_req(h, mode, rs, nreads, first_pair, npairs, s);
+	r.want_traceback = 1;
+	r.d_score = d_score; r.d_end_i = d_ei; r.d_end_j = d_ej; r.d_state = d_st;
+	r.d_ops = d_ops; r.d_ops_off = d_opsoff; r.d_nops = d_nops;
+	rc = align_device(h, r);
 	if (rc) return rc;
 	HIP_TRY(h, hipMemcpyAsync(out_score, d_score, (size_t)npairs * 4, hipMemcpyDeviceToHost, s));
 	if (out_end_i) HIP_TRY(h, hipMemcpyAsync(out_end_i, d_ei, (size_t)npairs * 4, hipMemcpyDeviceToHost, s));
@@ -3524,8 +3678,11 @@ static int allpairs_hit_slices(at_handle *h, int mode, int64_t nreads, const Rea
 		const int q = (int)(c & 1);
 		const int64_t lo = c * chunk, n = std::min(chunk, npairs - lo);
 		/* (slice c - 2, the last user of buffer set q, was delivered before slice c - 1 was queued) */
-		rc = align_device(h, mode, n, rs.d_words, rs.bits, rs.d_swoff, rs.d_len, rs.d_swoff, rs.d_len, rs.maxlen, rs.maxlen, 0, 0,
-		                  d_res[q][0], d_res[q][1], d_res[q][2], d_res[q][3], nullptr, nullptr, nullptr, s, nreads, first_pair + lo);
+		BatchReq r = triangle_req(h, mode, rs, nreads, first_pair + lo, n, s);
+		r.d_score = d_res[q][0]; r.d_end_i = d_res[q][1]; r.d_end_j = d_res[q][2]; r.d_state = d_res[q][3];
+		/* overlap: the bit-parallel bound with this call's threshold, whatever at_set_min_score says */
+		if (mode == AT_MODE_OVERLAP) { r.min_on = 1; r.min_score = threshold; }
+		rc = align_device(h, r);
 		if (rc) { (void)hipDeviceSynchronize(); return rc; }
 		if (c == 0) run.cfg0 = h->cfg;
 		at::PairHitsArgs pa;
@@ -3573,8 +3730,7 @@ static int pairhits_cigars(at_handle *h, int mode, const ReadSet &rs, const at::
 	da.score2 = w.sc; da.end_i2 = w.ei; da.end_j2 = w.ej; da.bad = w.bad;
 	HIP_TRY(h, at_pairhits_desc_launch(&da, h->ncu, s));
 	rc = scan_nops_device(h, n, w.aux, w.ops_off, s);
-	if (!rc) rc = align_device(h, mode, n, rs.d_words, rs.bits, w.woff1, w.len1, w.woff2, w.len2, rs.maxlen, rs.maxlen, 0, 1, w.sc, w.ei, w.ej, w.st,
-	                           w.ops, w.ops_off, w.nops, s, 0, 0);
+	if (!rc) rc = align_device(h, window_req(h, mode, n, rs, w, rs.maxlen, rs.maxlen, s));
 	if (rc) { (void)hipStreamSynchronize(s); return rc; }
 	if (tbcfg && tbcfg->empty()) *tbcfg = h->cfg;
 	rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, w.woff1, w.woff2, w.ei, w.ej, w.ops, w.ops_off, w.nops, flags, w.ncigar, w.stats, w.coff, w.cigar, dcap, s);
@@ -3623,12 +3779,7 @@ extern "C" int at_allpairs_hits(at_handle *h, int mode, int64_t nreads,
 		ReadSet rs;
 		int rc2 = upload_reads(h, mode, nreads, seq_blob, off, len, &rs);
 		if (rc2) return rc2;
-		{
-			/* overlap: the bit-parallel bound with this call's threshold, whatever at_set_min_score says; that setting is put back at once */
-			struct Keep { at_handle *h; int on, score; ~Keep() { h->min_on = on; h->min_score = score; } } keep = {h, h->min_on, h->min_score};
-			if (mode == AT_MODE_OVERLAP) { h->min_on = 1; h->min_score = threshold; }
-			rc2 = allpairs_hit_slices(h, mode, nreads, rs, first_pair, npairs, chunk_pairs, threshold, hits, run);
-		}
+		rc2 = allpairs_hit_slices(h, mode, nreads, rs, first_pair, npairs, chunk_pairs, threshold, hits, run);
 		if (rc2) return rc2;
 		config();
 		const int64_t nh = (int64_t)hits.size();

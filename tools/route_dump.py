@@ -1,17 +1,23 @@
 """Which kernel family, group width, rows per lane and storage class a fixed list of small batches takes: one JSON line per case
-with at_last_config, to compare two builds of the library on one card (`AT_LIB_PATH=... route_dump.py OUT.jsonl`; grids depend on
-the card).  Under a minute:
+with at_last_config and a checksum of the batch's results (score, end_i, end_j, state, nops and the op bytes in use), to compare two
+builds of the library on one card (`AT_LIB_PATH=... route_dump.py OUT.jsonl`; grids depend on the card): identical dumps are
+identical routing AND identical outputs.  Under a minute:
 
     uniform 150 x 150 and 1024 x 1024 in every mode (fit also with -s), 20 000 and 600 pairs, two scorings, with tracebacks
     ragged: the read lengths around every row-class edge (the lists of tests/test_gpu_parity.py: local, global / fit, long reads),
             1 400 pairs each, local / global / fit / fit -s / overlap with tracebacks, ACGT and ACGT + N
     edit at 64 / 160 / 1 000 bases, the number alone and with at_set_edit_traceback
+    edit infix (at_set_edit_infix) at 64 / 1 000 bases, the number alone and with the op lists
     one all-pairs overlap with at_set_min_score
+    the device entry without the uniform promise, 4 096 pairs of 150 x 150 (the device decides: "auto: [...]")
+    150 x 150 and 620 x 660 with tracebacks under the routing knobs of the packed path, one setting at a time
+(No batch here has more work items than resident waves: the last round's sliver as 32-lane items is tests/test_knobs.py's.)
 """
 import ctypes as C
 import json
 import os
 import sys
+import zlib
 
 import numpy as np
 
@@ -32,9 +38,22 @@ p = lambda a: a.ctypes.data_as(C.c_void_p)
 rng = np.random.default_rng(2609)
 
 
-def emit(case, cfg):
-    out.write(json.dumps({"case": case, "last_config": cfg}) + "\n")
+def emit(case, cfg, crc):
+    out.write(json.dumps({"case": case, "last_config": cfg, "results_crc32": "%08x" % crc}) + "\n")
     out.flush()
+
+
+def checksum(arrays, ops=None, ops_off=None, nops=None):
+    """CRC-32 over the result arrays and, of the op buffer, the bytes each pair's list uses"""
+    crc = 0
+    for a in arrays:
+        crc = zlib.crc32(np.ascontiguousarray(a).tobytes(), crc)
+    if ops is not None:
+        cnt = np.maximum(nops, 0).astype(np.int64)
+        start = np.cumsum(cnt) - cnt
+        idx = np.repeat(ops_off - start, cnt) + np.arange(int(cnt.sum()), dtype=np.int64)
+        crc = zlib.crc32(ops[idx].tobytes(), crc)
+    return crc
 
 
 def run(case, mode, blob, len1, len2, tb=True):
@@ -47,7 +66,8 @@ def run(case, mode, blob, len1, len2, tb=True):
     ops = np.zeros(int(tot.sum()) + 64, np.uint8)
     rc = lib.at_align_batch(al._h, A.MODES[mode], n, p(blob), p(off1), p(len1), p(off2), p(len2), 1 if tb else 0, p(score), p(ei), p(ej), p(st),
                             p(ops), p(off1), p(nops))
-    emit(case, al.last_config if rc == 0 else "error %d: %s" % (rc, lib.at_last_error(al._h).decode()))
+    emit(case, al.last_config if rc == 0 else "error %d: %s" % (rc, lib.at_last_error(al._h).decode()),
+         checksum((score, ei, ej, st, nops), ops, off1, nops))
     if rc:   # (nothing more on a device that may have faulted)
         sys.exit(1)
 
@@ -96,6 +116,18 @@ for l in (64, 160, 1000):
     run("edit ragged ..%d n=2000 alignments=1" % l, "edit", bases(int(lr.sum()) * 2 + 1), lr, lr)
 al.set_edit_traceback(False)
 
+# ---- edit infix: reads inside targets three times their length ----
+al.set_edit_infix(True)
+for l in (64, 1000):
+    n = 2000
+    len1, len2 = np.full(n, l, np.int32), np.full(n, 3 * l, np.int32)
+    blob = bases(n * 4 * l)
+    for etb in (False, True):
+        al.set_edit_traceback(etb)
+        run("edit infix %dx%d n=%d alignments=%d" % (l, 3 * l, n, etb), "edit", blob, len1, len2)
+al.set_edit_traceback(False)
+al.set_edit_infix(False)
+
 # ---- all-pairs overlap with a threshold ----
 for l in (100, 300, 1000):
     nreads = 300
@@ -105,7 +137,52 @@ for l in (100, 300, 1000):
     al.set_scoring(1, -2, -5, -1, -10, False, [])
     for T in (None, 20):
         al.set_min_score(T)
-        al.align_allpairs_stream("overlap", blob, off, lens, 0, nreads * (nreads - 1) // 2, 20000, lambda *a: None)
-        emit("all-pairs overlap %d reads of ..%d min_score=%s" % (nreads, l, T), al.last_config)
+        crc = [0]
+
+        def on_slice(first, *arrays):
+            crc[0] = checksum(arrays) ^ zlib.crc32(b"%d" % first, crc[0])
+        al.align_allpairs_stream("overlap", blob, off, lens, 0, nreads * (nreads - 1) // 2, 20000, on_slice)
+        emit("all-pairs overlap %d reads of ..%d min_score=%s" % (nreads, l, T), al.last_config, crc[0])
     al.set_min_score(None)
+
+# ---- the device entry without the uniform promise ----
+import torch
+
+dev = torch.device("cuda", 0)
+
+
+def run_device(case, mode, n, l1, l2, uniform):
+    seqs = bases(n * (l1 + l2)).tobytes()
+    pairs = [(seqs[k * (l1 + l2):k * (l1 + l2) + l1], seqs[k * (l1 + l2) + l1:(k + 1) * (l1 + l2)]) for k in range(n)]
+    words, woff1, woff2, len1, len2, bits = A.pack_pairs(pairs)
+    d = {k: torch.from_numpy(v).to(dev) for k, v in (("w", words.view(np.int32)), ("o1", woff1), ("o2", woff2), ("l1", len1), ("l2", len2))}
+    res = torch.zeros((5, n), dtype=torch.int32, device=dev)
+    ops = torch.zeros(n * (l1 + l2) + 64, dtype=torch.uint8, device=dev)
+    ops_off = torch.arange(n, dtype=torch.int64, device=dev) * (l1 + l2)
+    al.align_batch_device(A.MODES[mode], n, d["w"].data_ptr(), bits, d["o1"].data_ptr(), d["l1"].data_ptr(), d["o2"].data_ptr(), d["l2"].data_ptr(),
+                          l1, l2, uniform, True, res[0].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), res[3].data_ptr(), ops.data_ptr(),
+                          ops_off.data_ptr(), res[4].data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    o = res.cpu().numpy()
+    emit(case, al.last_config, checksum(tuple(o), ops.cpu().numpy(), ops_off.cpu().numpy(), o[4]))
+
+
+for name, mode, uj in MODES[:4]:
+    al.set_scoring(*SCORINGS["bench"], uj, SITES)
+    run_device("device entry, no uniform promise, 150x150 %s n=4096" % name, mode, 4096, 150, 150, False)
+
+# ---- the packed path's routing knobs, one setting at a time ----
+KNOBS = [{"AT_TWO_PASS": "2", "AT_TP_SPLIT": "0"}, {"AT_TWO_PASS": "2", "AT_TP_SPLIT": "1"}, {"AT_WALK_TEAMS": "0"}, {"AT_TAIL_SPLIT": "0"},
+         {"AT_CK_PIECE_PAIRS": "96"}, {"AT_TP_RESERVE": "2"}]
+for l1, l2 in ((150, 150), (620, 660)):
+    n = 20000
+    len1, len2 = np.full(n, l1, np.int32), np.full(n, l2, np.int32)
+    blob = bases(n * (l1 + l2))
+    for knobs in KNOBS:
+        os.environ.update(knobs)
+        for name, mode, uj in MODES[:4]:
+            al.set_scoring(*SCORINGS["bench"], uj, SITES)
+            run("knobs %s: uniform %dx%d %s n=%d" % (" ".join("%s=%s" % kv for kv in sorted(knobs.items())), l1, l2, name, n), mode, blob, len1, len2)
+        for k in knobs:
+            del os.environ[k]
 al.close()
