@@ -32,7 +32,7 @@ SCAN_SEP_READ = -1              # AT_SCAN_SEP_READ: min_sep of Aligner.scan_hits
 ABI_SYMBOLS = ["at_init", "at_destroy", "at_last_error", "at_set_scoring", "at_set_min_score", "at_set_edit_traceback", "at_set_edit_infix", "at_align_batch",
                "at_align_batch_device", "at_align_allpairs_device", "at_render_batch_device", "at_compact_ops_device",
                "at_align_batch_strings", "at_align_allpairs", "at_align_allpairs_stream", "at_search",
-               "at_search_strands", "at_scan", "at_scan_plan", "at_scan_local", "at_scan_local_plan", "at_scan_local_window", "at_scan_hits", "at_allpairs_hits", "at_revcomp", "at_revcomp_device",
+               "at_search_strands", "at_scan", "at_scan_plan", "at_scan_local", "at_scan_local_plan", "at_scan_local_window", "at_scan_fit", "at_scan_fit_plan", "at_scan_fit_window", "at_scan_hits", "at_allpairs_hits", "at_revcomp", "at_revcomp_device",
                "at_cigar", "at_cigar_batch_device", "at_align_batch_cigar",
                "at_comm_init", "at_comm_broadcast_scoring", "at_comm_allgather", "at_comm_destroy", "at_comm_abi_checked",
                "at_pack_words", "at_pack_batch", "at_render", "at_last_config"]
@@ -142,6 +142,12 @@ def load_library():
     lib.at_scan_local_plan.argtypes = [C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i64p, _i64p]
     lib.at_scan_local_window.restype = C.c_int64
     lib.at_scan_local_window.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.at_scan_fit.restype = C.c_int
+    lib.at_scan_fit.argtypes = lib.at_scan.argtypes
+    lib.at_scan_fit_plan.restype = C.c_int
+    lib.at_scan_fit_plan.argtypes = lib.at_scan_local_plan.argtypes
+    lib.at_scan_fit_window.restype = C.c_int
+    lib.at_scan_fit_window.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, _i64p, _i64p]
     lib.at_scan_hits.restype = C.c_int
     lib.at_scan_hits.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int64, C.c_int, C.c_int64] + [C.c_void_p] * 9 + [C.c_int64]
@@ -267,6 +273,32 @@ def scan_local_plan(len1, len2, m, u, o, e, min_score=None, tile_cols=0):
 def scan_local_window(end_i, end_j, score, m, u, o, e):
     """Host helper (at_scan_local_window): ws of a hit of Aligner.scan_local -- its alignment lies in the target columns (ws, end_j]."""
     return int(load_library().at_scan_local_window(int(end_i), int(end_j), int(score), int(m), int(u), int(o), int(e)))
+
+
+def scan_fit_plan(len1, len2, m, u, o, e, min_score=None, tile_cols=0):
+    """Host helper (at_scan_fit_plan): how Aligner.scan_fit cuts a pair of len1 x len2 under the scoring m / u / o / e --
+    (tile, overlap, ntiles, nfull): the end columns a tile owns (tile n: n * tile <= j < (n + 1) * tile), the columns in front of
+    them, the tiles of the target (0 for len2 < len1) and how many of them (the leading ones) have the full shape
+    len1 x (tile + overlap).  Tile n sweeps the target columns (max(0, n * tile - overlap), min(len2, that + tile + overlap)]; the
+    tiles 1 .. min(ntiles - 1, overlap // tile) would repeat tile 0's sweep and are not swept."""
+    lib = load_library()
+    tile, ov, nt, nf = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    rc = lib.at_scan_fit_plan(int(len1), int(len2), 0 if min_score is None else 1, 0 if min_score is None else int(min_score),
+                              int(tile_cols), int(m), int(u), int(o), int(e), C.byref(tile), C.byref(ov), C.byref(nt), C.byref(nf))
+    if rc:
+        raise AlignToolsError(rc, lib.at_last_error(None).decode())
+    return tile.value, ov.value, nt.value, nf.value
+
+
+def scan_fit_window(end_j, score, len1, len2, m, u, o, e):
+    """Host helper (at_scan_fit_window): (ws, we) of a hit of Aligner.scan_fit -- the fit pair (query, target columns (ws, we]) has
+    the hit's score and state, the end column end_j - ws and its ops."""
+    lib = load_library()
+    ws, we = C.c_int64(0), C.c_int64(0)
+    rc = lib.at_scan_fit_window(int(end_j), int(score), int(len1), int(len2), int(m), int(u), int(o), int(e), C.byref(ws), C.byref(we))
+    if rc:
+        raise AlignToolsError(rc, lib.at_last_error(None).decode())
+    return ws.value, we.value
 
 
 def cigar(ops, s1, end_i, s2, end_j, extended=True):
@@ -562,7 +594,7 @@ class Aligner:
         return self._scan_call("at_scan", queries, targets, k, cutoff, strands, cigar, cigar_m, tile_cols)
 
     def _scan_call(self, entry, queries, targets, k, cutoff, strands, cigar, cigar_m, tile_cols):
-        """at_scan / at_scan_local: one argument list, one layout of the results"""
+        """at_scan / at_scan_local / at_scan_fit: one argument list, one layout of the results"""
         if strands not in STRANDS:
             raise ValueError("strands must be one of %s" % ", ".join(sorted(STRANDS)))
         qs = [_b(x) for x in queries]
@@ -615,6 +647,17 @@ class Aligner:
         cigar as scan() lays them out.  tile_cols: the columns a tile owns (a multiple of 16; 0: the default) -- the results do not
         depend on it."""
         return self._scan_call("at_scan_local", queries, targets, k, min_score, strands, cigar, cigar_m, tile_cols)
+
+    def scan_fit(self, queries, targets, k=1, min_score=None, strands="forward", cigar=False, cigar_m=False, tile_cols=0):
+        """End-to-end affine alignment of reads against long targets (at_scan_fit): for every query the best `k` hits over the
+        targets, one per (query, strand, target), a hit being exactly what align_batch("fit", ...) returns without jump sites for
+        (query or its reverse complement, target) -- score, end cell (len(query), j*), state ST_MID or ST_LOW -- with no bound on
+        the target length; a target shorter than the query is no candidate.  Scoring with m >= 1, o <= -1, e <= -1, no jump sites;
+        queries of 1 .. 1 024 bases.  min_score keeps only hits with score >= min_score.  Returns what scan() returns: the dict of
+        search("fit", ...) (end_j is the absolute column; `strand` with "reverse" / "both") and, with cigar=True, stats, ncigar and
+        cigar as scan() lays them out.  tile_cols: the end columns a tile owns (a multiple of 16; 0: the default) -- the results
+        do not depend on it."""
+        return self._scan_call("at_scan_fit", queries, targets, k, min_score, strands, cigar, cigar_m, tile_cols)
 
     def scan_hits(self, queries, targets, max_dist, min_sep=SCAN_SEP_READ, strands="forward", cigar=False, cigar_m=False, tile_cols=0,
                   cand_cap=0):

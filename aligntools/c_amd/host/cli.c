@@ -164,6 +164,8 @@ static int main_single(int cmd, int argc, char *argv[])
  *                    hits of `batch local --queries` with no bound on the target length; --score-only prints their hit lines,
  *                    --paf their PAF lines.  --best, --both-strands and --min-score as with --queries.  Queries of up to 1 024
  *                    bases; -m >= 1, -o <= -1, -e <= -1.  Not with --all-vs-all, --gpus N > 1, --scan, --infix, --keep.
+ *                    With `fit` instead of `local` (at_scan_fit): the hits of `batch fit --queries` -- the whole read, both ends of
+ *                    the target free -- in the same output form; not with -s (jump sites are per-target columns).
  *     --all-hits D   (with --scan) EVERY occurrence of every read with at most D edits (at_scan_hits) instead of the best K hits:
  *                    --score-only prints "query\ttarget\tedit_distance=d\tend=J" per hit (J the absolute end column; "\t+" / "\t-"
  *                    with --both-strands), --paf the PAF line of --scan.  --min-sep S keeps an occurrence only if no better one
@@ -820,8 +822,9 @@ static int batch_search(int cmd, opt_t *opt, const batch_flags *bf, const char *
 
 /* ---- --scan (edit -u 1 --infix --queries): reads against long targets, the best K hits of each query (at_scan) ----
  * --score-only prints the hit lines of the --queries form, --paf its PAF lines; the CIGARs come with the hits, from the same call.
- * --long-targets (local --queries) is the same form over at_scan_local: scores instead of distances, --min-score as its cutoff. */
-static int batch_scan(opt_t *opt, const batch_flags *bf, const char *qfile, const char *tfile)
+ * --long-targets (local --queries) is the same form over at_scan_local: scores instead of distances, --min-score as its cutoff;
+ * fit_mode: over at_scan_fit (fit --queries). */
+static int batch_scan(opt_t *opt, const batch_flags *bf, int fit_mode, const char *qfile, const char *tfile)
 {
 	at_reader *rq = at_reader_open(qfile), *rt;
 	at_chunk c;
@@ -862,7 +865,7 @@ static int batch_scan(opt_t *opt, const batch_flags *bf, const char *qfile, cons
 	for (pass = 0; pass < 2; ++pass) {       /* a second call if the hits have more runs than the first guess */
 		if (bf->paf) { free(cg); cg = (uint32_t *)at_xmalloc((size_t)cap * 4); }
 		if (bf->long_targets) {
-			rc = at_scan_local(h, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, bf->min_on, bf->min_score,
+			rc = (fit_mode ? at_scan_fit : at_scan_local)(h, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, bf->min_on, bf->min_score,
 			                   bf->both ? AT_STRAND_BOTH : AT_STRAND_FWD, 0, 0, tgt, sc, ei, ej, st, sd, nh, stats, ncg, cgoff, cg, cap);
 		} else {
 			rc = at_scan(h, nq, c.blob, qoff, qlen, nt, c.blob, toff, tlen, kb, 0, 0, bf->both ? AT_STRAND_BOTH : AT_STRAND_FWD, 0, 0,
@@ -1054,7 +1057,7 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	/* --queries: refused with what it cannot go with, before any GPU call */
 	{
 		const char *why = NULL;
-		if (bf.long_targets && cmd != C_LOCAL) why = "--long-targets goes with local";
+		if (bf.long_targets && cmd != C_LOCAL && cmd != C_FIT) why = "--long-targets goes with local";
 		else if (bf.long_targets && !bf.queries) why = "--long-targets goes with --queries (reads against long targets)";
 		else if (bf.long_targets && bf.all_vs_all) why = "--long-targets does not go with --all-vs-all";
 		else if (bf.long_targets && bf.gpus > 1) why = "--long-targets runs on one GPU: it does not go with --gpus N > 1";
@@ -1103,11 +1106,14 @@ static int main_batch(int argc, char *argv[], char *argv0)
 	if (optind + 1 > n - 1) { cmd_usage(cmd, opt); free(opt); free(av); return 1; }
 	if (bf.alignments && opt->u != 1) { fprintf(stderr, "--alignments needs -u 1\n%s", usage_line); free(opt); free(av); return 1; }
 	if (bf.infix && opt->u != 1) { fprintf(stderr, "--infix needs -u 1\n%s", usage_line); free(opt); free(av); return 1; }
+	if (bf.long_targets && cmd == C_FIT && opt->s == AT_TRUE) {
+		fprintf(stderr, "fit --long-targets does not go with -s (jump sites are per-target columns)\n%s", usage_line); free(opt->sites.pos); free(opt); free(av); return 1;
+	}
 	g_edit_alignments = bf.alignments;
 	g_edit_infix = bf.infix;
 	if (bf.queries) {
 		k = bf.all_hits ? batch_scan_hits(opt, &bf, bf.queries, av[n - 1])
-		  : bf.scan || bf.long_targets ? batch_scan(opt, &bf, bf.queries, av[n - 1]) : batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
+		  : bf.scan || bf.long_targets ? batch_scan(opt, &bf, cmd == C_FIT, bf.queries, av[n - 1]) : batch_search(cmd, opt, &bf, bf.queries, av[n - 1]);
 		free(opt->sites.pos); free(opt); free(av);
 		return k;
 	}

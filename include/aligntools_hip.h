@@ -471,6 +471,56 @@ int at_scan_local_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutof
 int64_t at_scan_local_window(int32_t end_i, int64_t end_j, int32_t score, int m, int u, int o, int e);
 
 /*
+ * End-to-end affine alignment of reads against LONG targets: what at_search_strands(AT_MODE_FIT) delivers -- for each
+ * query the best k hits (1 <= k <= 64) over the targets, one per (query, strand, target), a hit being exactly what
+ * at_align_batch(AT_MODE_FIT) returns, use_jump off, for (query or its reverse complement, target): the whole query, both ends of the
+ * target free, affine gaps; the score, the end cell (l1, j*) and the start state AT_ST_MID or AT_ST_LOW (M before L at equal score,
+ * then the smallest column; the target's last column is left out of the end scan) -- with no bound on the target length (any int32).
+ * A target shorter than the query is no candidate, and that is no error.  A target is cut into overlapping tiles that are swept as
+ * ordinary fit pairs by the batch kernels; the best over the tiles is exact for every pair that scores >= c = max(cutoff, lb),
+ * lb = min(m, u) * l1 + o + e being a score every candidate reaches (without a cutoff every pair is exact; the other pairs are no hits
+ * under the cutoff anyway).
+ *   domain: the handle's scoring with m >= 1, o <= -1, e <= -1 (u anything), use_jump off; queries of 1 .. 1 024 bases; any alphabet
+ *   at_search takes; one GPU
+ *   rank: higher score first, then the smaller target index, then strand 0 before strand 1 (at_search_strands' order)
+ *   out_target .. out_nhits as in at_search_strands; end_j is the ABSOLUTE column j* of the target
+ *   tile_cols: the end columns a tile owns, a multiple of 16; 0 = the library's default (1 024).  The results do not depend on it
+ *   the four CIGAR outputs are either all NULL or laid out as in at_scan (an unused entry: 0 runs, a row of -1, no room).  The ops of a
+ *   hit are those of the reference's walk on the full table; AT_CG_START_J is absolute.  They are made in a window of the target, and
+ *   a window that does not reproduce its hit's score, state and end column is AT_ERR_RANGE, never a silent result
+ * at_set_min_score and the edit settings neither matter nor change.  Synchronous.  nq == 0 writes nothing; nt == 0 gives every query 0
+ * hits.  AT_ERR_DOMAIN: the scoring, use_jump set (site lists are per-target columns), an empty or too long query, a handle of a
+ * multi-process job, a candidate pair on which fit is not defined (a query of one base against a target of one base);
+ * AT_ERR_ARG: k outside 1..64, strands outside 1..3, tile_cols negative or no multiple of 16.  AT_ERR_RANGE, before anything is swept:
+ * a tile is a pair of the batch entry and has its exact-score bound, max(|m|,|u|,|o|,|e|,|j|) * (l1 + min(longest target, T + ov) + 2)
+ * < 2^24 with ov = round16up(l1 + floor((max(m,u) * l1 - c) / min(|o|,|e|)) + 1).
+ * at_last_config: "scan-fit: tile=T overlap=OV tiles=N strands=fwd|rev|both, B blocks, S slices, k=K; " + the first slice's sweep text
+ * + " sweep=..ms" (the device time of the sweep phase, as at_scan reports it) and, with CIGARs, "; windows: " and the window pass's
+ * text.  OV is the largest overlap of the call's query lengths.
+ */
+int at_scan_fit(at_handle *h,
+                int64_t nq, const uint8_t *q_blob, const int64_t *q_off, const int32_t *q_len,
+                int64_t nt, const uint8_t *t_blob, const int64_t *t_off, const int32_t *t_len,
+                int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile_cols, int flags,
+                int32_t *out_target, int32_t *out_score, int32_t *out_end_i, int32_t *out_end_j,
+                int32_t *out_state, int32_t *out_strand, int32_t *out_nhits,
+                int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
+                uint32_t *out_cigar, int64_t cigar_cap);
+/* Host helper (no handle, no GPU): how at_scan_fit cuts a pair of len1 x len2 under the scoring m / u / o / e -- *tile = the end columns
+ * a tile owns (tile n: n tile <= j < (n + 1) tile), *overlap = ov, the columns in front of them, *ntiles = ceil(len2 / tile), or 0 for
+ * len2 < len1, *nfull = the leading tiles of the full shape len1 x (tile + ov).  Tile n sweeps the columns (max(0, n tile - ov),
+ * min(len2, that + tile + ov)]; the tiles 1 .. min(ntiles - 1, ov / tile) would repeat tile 0's sweep and are not swept.  Any out
+ * pointer may be NULL.  AT_ERR_ARG for a negative length and a bad tile_cols, AT_ERR_DOMAIN for the scoring, the query, or
+ * tile + ov >= 2^31. */
+int at_scan_fit_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutoff, int32_t tile_cols, int m, int u, int o, int e,
+                     int32_t *tile, int32_t *overlap, int64_t *ntiles, int64_t *nfull);
+/* Host helper: the window (*ws, *we] of a hit of at_scan_fit that ends in column end_j with this score -- the fit pair (query, target
+ * columns (ws, we]) has the hit's score and state, the end column end_j - ws and its ops; ws is a multiple of 16,
+ * ws <= end_j < we <= len2 and we - ws >= len1.  AT_ERR_DOMAIN for the scoring or the query, AT_ERR_ARG for len2 < len1 or an end_j
+ * outside 0 .. len2 - 1. */
+int at_scan_fit_window(int64_t end_j, int32_t score, int32_t len1, int32_t len2, int m, int u, int o, int e, int64_t *ws, int64_t *we);
+
+/*
  * EVERY occurrence of a read under a distance cutoff: at_scan keeps one hit per (query, strand, target); this entry
  * reports every one.  For a query of l1 >= 1 bases, a target of l2 bases and max_dist >= 0 let c = min(max_dist, l1 - 1) (a match
  * must cost less than deleting the whole read; a query of length 0 has no hits) and D the table of at_scan, D(0,j) = 0, D(i,0) = i.
