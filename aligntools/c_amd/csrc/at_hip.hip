@@ -1535,14 +1535,20 @@ static int launch_packed(at_handle *h, const BatchReq &r, int kmode, bool tb, co
 		b.only_if = r.only_if; b.only_val = r.only_val;
 		b.off_refb = P.off_refb; b.off_bound = P.off_bound; b.ptr_lanes = P.ptr_lanes; b.off_sm = P.off_sm; b.nsm = P.nsm;
 		Plan pl;
-		char tag16[128];
+		char tag16[192];
 		snprintf(tag16, sizeof tag16, "packed16 x%d bits=%d %dx%d-lane groups (%d pairs/wave)%s", 1 << ts, bits, 64 / P.g, P.g, per_wave,
 		         rag ? " ragged frames" : "");
 		if (two_pass) snprintf(tag16 + strlen(tag16), sizeof tag16 - strlen(tag16), " two-pass%s ck=%d", tp_split ? " (walk kernel)" : "", at::ck_steps(P.g));
 		/* local 2-bit batches with scores x16 whose scoring allows it (m >= 0 >= u, (m - u) * 16 in a byte) run the kernels with the
 		 * profile lookup (at_sweep16.hip.h, PROF): the same results, 0.84 of an instruction per row-step less.  Every other scoring
-		 * keeps the kernels with the score LUT */
-		const bool prof = kmode == at::K_LOCAL && bits == 2 && ts == 4 && at::profile_lookup_ok(h->m, h->u);
+		 * keeps the kernels with the score LUT.  With tracebacks in one pass those kernels also take the cell maximum with one three-input
+		 * float maximum on biased scores, which holds the batch's frame to max3_domain_ok (m * min(l1, l2) <= 944 and |o| + |u| + |e| <= 959):
+		 * a batch outside it keeps the LUT kernels too */
+		const bool prof = kmode == at::K_LOCAL && bits == 2 && ts == 4 && at::profile_lookup_ok(h->m, h->u) &&
+		                  (!(tb && !two_pass) || at::max3_domain_ok(h->m, h->u, h->o, h->e, max_len1, max_len2));
+		/* (which form ran, for at_last_config and tools/route_dump.py) */
+		if (kmode == at::K_LOCAL && ts == 4)
+			snprintf(tag16 + strlen(tag16), sizeof tag16 - strlen(tag16), "%s", !prof ? " [score LUT]" : tb && !two_pass ? " [profile words, biased max3]" : " [profile words]");
 		auto pick = [&](int st) {
 			if (two_pass) return st == 1 ? at_pick16_tp(kmode, P.g, P.k, ts, bits, tp_split, prof) : (at_sweep16_fn) nullptr;
 			return rag ? at_pick16_rag(kmode, P.g, P.k, st, tb, bits, prof) : at_pick16(kmode, P.g, P.k, ts, st, tb, bits, prof);

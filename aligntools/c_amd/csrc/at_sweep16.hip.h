@@ -381,6 +381,108 @@ AT_DEV uint32_t prof_m_v(uint32_t diag, uint32_t pb, uint32_t pa, uint32_t psel,
 	asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(m) : "v"(t), "s"(nu2));
 	return m;
 }
+/* The PROF kernels that keep tracebacks in one pass (MAX3 in sweep16_items) take the cell maximum X = max(L, M, U) with ONE instruction,
+ * gfx950's v_pk_maximum3_f16 (same issue class as v_pk_max_i16: tools/valu_issue.hip).  Halves in [0x0400, 0x7BFF] are the positive normal
+ * f16 numbers, whose float order is the order of their bit patterns, so the IEEE maximum of three of them is their integer maximum, tag
+ * nibble included.  Local L and U go down to o * 16 < 0 -- NaN patterns -- so the L, U and X domain carries the bias B = 0x4000 in every
+ * half, from the borders to the end, at no instruction's cost:
+ *   Mraw  diag is X + B now; prof_m_v subtracts |u| * 16 + B instead of |u| * 16 and returns the UNBIASED candidate, bit for bit what it was
+ *         (value, tag nibble, 0x0000 for HOME), which the pointer cell and the arg-max key read as before;
+ *   Mc    = v_and_or(Mraw, clean, tagM | B): Mraw < 0x4000, so the OR is the add;
+ *   Lc, Uc, Mo, Ld, Uraw  unchanged: sums and integer maxima of biased values are biased, and no signed packed add saturates.
+ * The host sends a batch here only if every half that reaches the instruction lies in that range (max3_domain_ok, with hi = m * min(l1, l2)
+ * the largest score of the matrix): B + 16 * hi + 15 + 240 <= 0x7BFF -- the 240 keeps prof_m_v's sum diag + S' in range as well -- and
+ * B - 16 * (|o| + |u| + |e|) - 15 >= 0x0400, below the lowest local L or U (packed_ok: no cell under o).  Batches outside keep the LUT kernels.
+ * (Rows between l1 and the end of the last lane that owns rows repeat the read's last base and may score past hi; they feed only rows
+ * further down, never a row of the matrix, and their arg-max keys are masked: what the instruction makes of them is never read.) */
+constexpr uint32_t kMax3Bias = 0x4000u, kMax3Lo = 0x0400u, kMax3Hi = 0x7BFFu;
+constexpr long long max3_abs(long long v) { return v < 0 ? -v : v; }
+/* the lowest and the highest half that reaches the instruction, from the scoring and the shape */
+constexpr long long max3_low(int u, int o, int e) { return (long long)kMax3Bias - 16 * (max3_abs(o) + max3_abs(u) + max3_abs(e)) - 15; }
+constexpr long long max3_high(int m, int l1, int l2) { return (long long)kMax3Bias + 16 * ((long long)m * (l1 < l2 ? l1 : l2)) + 15; }
+__host__ __device__ constexpr bool max3_domain_ok(int m, int u, int o, int e, int l1, int l2)
+{
+	return profile_lookup_ok(m, u) && o <= 0 && e <= 0 && l1 >= 1 && l2 >= 1 &&
+	       max3_high(m, l1, l2) + 240 <= (long long)kMax3Hi && max3_low(u, o, e) >= (long long)kMax3Lo;
+}
+/* a finite f16 as an integer multiple of 2^-24 (sign, 5 exponent bits, 10 mantissa bits), and the IEEE maximum of three: NaN if any is */
+constexpr long long f16_scaled(uint32_t h)
+{
+	const long long ex = (h >> 10) & 31u, mant = h & 0x3ffu;
+	const long long v = ex == 0 ? mant : (1024 + mant) << (ex - 1);
+	return (h & 0x8000u) ? -v : v;
+}
+constexpr bool f16_nan(uint32_t h) { return ((h >> 10) & 31u) == 31u && (h & 0x3ffu) != 0; }
+constexpr uint32_t max3f_half(uint32_t a, uint32_t b, uint32_t c)
+{
+	if (f16_nan(a) || f16_nan(b) || f16_nan(c)) return 0x7e00u;
+	const uint32_t ab = f16_scaled(a) >= f16_scaled(b) ? a : b;
+	return f16_scaled(ab) >= f16_scaled(c) ? ab : c;
+}
+constexpr uint32_t max3i_half(uint32_t a, uint32_t b, uint32_t c)   /* pmax(pmax(a, b), c) of one half */
+{
+	const int x = (int)(short)a, y = (int)(short)b, z = (int)(short)c;
+	const int xy = x > y ? x : y;
+	return (uint32_t)(xy > z ? xy : z) & 0xffffu;
+}
+/* the route condition gives the domain: at the ends of every admitted range the halves lie in [0x0400, 0x7BFF], one step outside they need not */
+constexpr bool max3_domain_proof()
+{
+	for (int m = 0; m <= 15; ++m) {
+		const int lmax = m ? 944 / m : 4096;                     /* the last admitted min(l1, l2) */
+		if (!max3_domain_ok(m, m - 15, -1, -1, lmax, 4096) || max3_high(m, lmax, 4096) + 240 > (long long)kMax3Hi) return false;
+		if (m && max3_domain_ok(m, m - 15, -1, -1, lmax + 1, lmax + 1)) return false;
+	}
+	/* |o| + |u| + |e| = 959 is the last sum admitted */
+	if (!max3_domain_ok(2, -2, -955, -2, 150, 150) || max3_low(-2, -955, -2) < (long long)kMax3Lo || max3_domain_ok(2, -2, -956, -2, 150, 150)) return false;
+	if (!max3_domain_ok(2, -2, -2, -1, 472, 500) || max3_domain_ok(2, -2, -2, -1, 473, 500) || !max3_domain_ok(2, -2, -60, -2, 150, 150)) return false;
+	return !max3_domain_ok(8, -8, -2, -1, 10, 10) && !max3_domain_ok(2, -2, 1, -1, 10, 10);
+}
+static_assert(max3_domain_proof(), "biased maximum: the route condition keeps every half the instruction reads in [0x0400, 0x7BFF]");
+/* on the domain the three-input float maximum is the integer maximum of the tagged halves -- L (12) beats M (6) beats U (3) on equal
+ * values, a larger value beats any tag: the corner values of the domain and their neighbours, every order of the three tags */
+constexpr bool max3_order_proof(int p)   /* p: which of the six orders of the three tags */
+{
+	const uint32_t vals[] = {kMax3Lo, kMax3Lo + 16, 0x07f0u, 0x0800u, kMax3Bias - 16, kMax3Bias, kMax3Bias + 16, 0x43f0u, 0x4400u, 0x7be0u, 0x7bf0u};
+	const uint32_t perm[6][3] = {{12u, 6u, 3u}, {12u, 3u, 6u}, {6u, 12u, 3u}, {6u, 3u, 12u}, {3u, 12u, 6u}, {3u, 6u, 12u}};
+	for (uint32_t a : vals)
+		for (uint32_t b : vals)
+			for (uint32_t c : vals) {
+				const uint32_t x = a | perm[p][0], y = b | perm[p][1], z = c | perm[p][2];
+				if (x < kMax3Lo || y < kMax3Lo || z < kMax3Lo || x > kMax3Hi || y > kMax3Hi || z > kMax3Hi) return false;
+				if (max3f_half(x, y, z) != max3i_half(x, y, z)) return false;
+			}
+	/* equal values: the tag decides, L > M > U, wherever it stands */
+	for (uint32_t v : vals)
+		if (max3f_half(v | perm[p][0], v | perm[p][1], v | perm[p][2]) != (v | 12u) || max3f_half(v | 3u, v | (p & 1 ? 6u : 3u), v | 6u) != (v | 6u)) return false;
+	/* and outside the domain the instruction is no integer maximum: an unbiased o * 16 is a NaN pattern */
+	return max3f_half(0xffe0u, 0x0006u, 0x0003u) == 0x7e00u && max3i_half(0xffe0u, 0x0006u, 0x0003u) == 0x0006u;
+}
+#define AT_MAX3_ORDER(p) static_assert(max3_order_proof(p), "biased maximum: on [0x0400, 0x7BFF] the IEEE maximum of three halves is their integer maximum, tags L > M > U included");
+AT_MAX3_ORDER(0) AT_MAX3_ORDER(1) AT_MAX3_ORDER(2) AT_MAX3_ORDER(3) AT_MAX3_ORDER(4) AT_MAX3_ORDER(5)
+#undef AT_MAX3_ORDER
+/* Mraw from the biased diagonal: add, subtract |u| * 16 + B and clamp equals pmax(padd(X, S), 0) of the unbiased X, bit for bit, for every
+ * X of the admitted range with any tag nibble */
+constexpr bool max3_m_proof(int m, int u, uint32_t lo, uint32_t hi)
+{
+	if (!profile_lookup_ok(m, u)) return false;
+	const int m16 = m * 16, u16 = u * 16;
+	const uint32_t d = (uint32_t)(m16 - u16), nu = (uint32_t)(-u16) + kMax3Bias;
+	for (uint32_t x = lo; x < hi && x + kMax3Bias + 240 <= kMax3Hi; ++x)
+		if (prof_m_half(x + kMax3Bias, d, nu) != old_m_half(x, m16) || prof_m_half(x + kMax3Bias, 0u, nu) != old_m_half(x, u16)) return false;
+	return true;
+}
+#define AT_MAX3_PROOF_(m, u, lo, hi) static_assert(max3_m_proof(m, u, lo, hi), "biased maximum: the diagonal candidate is what it was, bit for bit");
+#define AT_MAX3_PROOF(m, u) AT_MAX3_PROOF_(m, u, 0u, 0x1000u) AT_MAX3_PROOF_(m, u, 0x1000u, 0x2000u) AT_MAX3_PROOF_(m, u, 0x2000u, 0x3000u) AT_MAX3_PROOF_(m, u, 0x3000u, 0x3c00u)
+AT_MAX3_PROOF(0, 0) AT_MAX3_PROOF(15, 0) AT_MAX3_PROOF(0, -15) AT_MAX3_PROOF(8, -7) AT_MAX3_PROOF(2, -2)
+#undef AT_MAX3_PROOF_
+#undef AT_MAX3_PROOF
+AT_DEV uint32_t pmax3f(uint32_t a, uint32_t b, uint32_t c)
+{
+	uint32_t d;
+	asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+	return d;
+}
 /* the four s2 codes of a sequence byte as staged bytes: the code, or 8 * the code for the PROF kernels */
 template <bool PROF>
 AT_DEV uint32_t s2_bytes(uint32_t b)
@@ -886,6 +988,11 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 	 * instead of five -- removed 4.8 M instructions of a C2 launch and made it 5 % slower: profiles/LOG.md I.) */
 	constexpr bool DIET = MODE == K_LOCAL && TS == 4 && CK == 0 && G < 64;
 	constexpr bool CBORD = DIET && (AT_LOCAL_DIET & 1), TSC = DIET && (AT_LOCAL_DIET & 2);
+	/* MAX3: the one-pass local kernels with the profile lookup and tracebacks take X = max(L, M, U) with one v_pk_maximum3_f16 on scores
+	 * that carry the bias B in the L, U and X domain (pmax3f above; the host sends a batch here only if max3_domain_ok).  Their retags
+	 * are the v_and_or that carries B into the diagonal candidate; the scores-only kernels have none and keep their two maxima. */
+	constexpr bool MAX3 = X3 && PROF && TB;
+	constexpr int BIAS = MAX3 ? (int)kMax3Bias : 0;   /* on every border value of L, U and X */
 	/* Jump state with scores x16: the cell keeps the 4 bits of the other modes and the jump state's own pointer (did J open from
 	 * M here?) goes to a BIT PLANE beside the cells -- one word per 4 rows x 4 steps and half -- 5 bits per cell instead of the 8 of a
 	 * byte cell.  (Scores x4 carry score bits in the low nibble of J: they keep the byte cells.) */
@@ -922,7 +1029,7 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 	uint32_t oL2 = pk2(a.o16 | 3), oR2 = pk2(a.o16 | 1);                    /* overlap: gap + LEFT / RIGHT tag (o16 is a multiple of 4) */
 	asm volatile("" : "+v"(oL2), "+v"(oR2));
 	/* constants live in VGPRs: VOP3 encodings take no 32-bit literals, and a literal would split and_or into two ops */
-	uint32_t cClean = (uint32_t)(0xffff & ~TMASK) * 0x00010001u, cTagM = (uint32_t)TGM * 0x00010001u;
+	uint32_t cClean = (uint32_t)(0xffff & ~TMASK) * 0x00010001u, cTagM = (uint32_t)(TGM | BIAS) * 0x00010001u;   /* (MAX3: Mc = Mraw + B by the retag) */
 	uint32_t cTagL = (uint32_t)TGL * 0x00010001u, cTagU = (uint32_t)TGU * 0x00010001u;
 	uint32_t cM3 = 0x00030003u, cM7 = 0x00070007u, cNib = 0x000f000fu, cF0 = 0x00f000f0u, cF000 = 0xf000f000u;
 	uint32_t c8888 = 0x88888888u, c3333 = 0x33333333u;
@@ -939,7 +1046,7 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 	asm volatile("" : "+v"(c1), "+v"(umm2), "+v"(m2));
 	if constexpr (PROF) lut_lo = (uint32_t)(a.m16 - a.u16);   /* PROF: D takes a register of the LUT; |u| * 16 rides in a scalar one (prof_m_v) */
 	const uint32_t &profD = lut_lo;
-	const uint32_t nu2 = pk2(-a.u16);
+	const uint32_t nu2 = pk2(-a.u16 + BIAS);   /* (MAX3: the biased diagonal gives up B with |u| * 16) */
 	(void)profD; (void)nu2;
 	/* (CBORD kernels: the gap scores ride in scalar registers, one scalar operand per packed add.  With them in vector registers the
 	 * 8-lane kernel with pointers keeps a 64-byte stack slot of a spilled argument tuple that no instruction touches -- a private segment
@@ -1067,7 +1174,7 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 				int x = imax3(L | TGL, M | TGM, U | TGU);
 				const int ld = imax(sat16((L | TGL) + e16), sat16((M | TGM) + o16));
 				if constexpr (OVL) x = j == 0 ? 0 : kNeg16;        /* M(0,j) = -inf, then M(i,0) = 0 for all i (:937-938) */
-				mem.st2(a.off_bound + 2 * j, pk2(x), pk2(ld));
+				mem.st2(a.off_bound + 2 * j, pk2(x + BIAS), pk2(ld + BIAS));
 			}
 		}
 		/* CBORD: the same two words in every column -- what the loop above would store for a local matrix */
@@ -1076,8 +1183,8 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 		if constexpr (CBORD) {
 			int L, M, U;
 			border16<MODE>(0, 1, o16, e16, L, M, U);
-			bxC = pk2(imax3(L | TGL, M | TGM, U | TGU));
-			blC = pk2(imax(sat16((L | TGL) + e16), sat16((M | TGM) + o16)));
+			bxC = pk2(imax3(L | TGL, M | TGM, U | TGU) + BIAS);
+			blC = pk2(imax(sat16((L | TGL) + e16), sat16((M | TGM) + o16)) + BIAS);
 		}
 		mem.sync();
 
@@ -1122,12 +1229,12 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 				int L, M, U;
 				border16<MODE>(i0 + r + 1, 0, o16, e16, L, M, U);
 				L = sat16(L);
-				Mo_l[r] = pk2(sat16((M | TGM) + o16));
-				U_l[r] = pk2(U | TGU);
+				Mo_l[r] = pk2(sat16((M | TGM) + o16) + BIAS);
+				U_l[r] = pk2((U | TGU) + BIAS);
 				L_l[r] = pk2(L | TGL);
 				if constexpr (ISFIT) Lrow = L_l[r];       /* (fit: the same border value in every row) */
 				J_l[r] = neg2;                    /* J is -inf on both borders (:616, :622) */
-				Xl[0][r] = pk2(imax3(L | TGL, M | TGM, U | TGU));
+				Xl[0][r] = pk2(imax3(L | TGL, M | TGM, U | TGU) + BIAS);
 				if constexpr (OVL) Xl[0][r] = 0;  /* M(i,0) = 0 */
 				Xl[1][r] = Xl[0][r];
 			}
@@ -1148,7 +1255,7 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 				int L, M, U;
 				border16<MODE>(base, 0, o16, e16, L, M, U);
 				L = sat16(L);
-				Ad = pk2(imax3(L | TGL, M | TGM, U | TGU));
+				Ad = pk2(imax3(L | TGL, M | TGM, U | TGU) + BIAS);
 				if constexpr (OVL) Ad = 0;
 			}
 			uint32_t best[NCH], bt[NCH];           /* local: per-lane (key, step) of this strip, per chain of rows */
@@ -1316,7 +1423,9 @@ AT_DEV long long sweep16_items(const Sweep16Args &a, long long wnext, const long
 							const uint32_t Uraw = pmax(Mo_l[r], padd(U_l[r], e2));
 							const uint32_t Uc = TB ? vandor(Uraw, cClean, cTagU) : Uraw;
 							const uint32_t Mo = padd(Mc, o2);
-							uint32_t Xo = pmax(pmax(Lc, Mc), Uc);
+							uint32_t Xo;
+							if constexpr (MAX3) Xo = pmax3f(Lc, Mc, Uc);   /* one instruction: biased halves are positive normal f16 */
+							else Xo = pmax(pmax(Lc, Mc), Uc);
 							uint32_t Jraw = 0;
 							if constexpr (HASJ) {
 								Jraw = pmax(padd(Mo_l[r], gopen), J_l[r]);     /* M first: tag 10 beats J's tag 0 on ties */

@@ -112,6 +112,7 @@ KERNEL(v_pk_lshlrev_b16, A2("v_pk_lshlrev_b16", ""))
 KERNEL(v_pk_ashrrev_i16, A2("v_pk_ashrrev_i16", ""))
 KERNEL(v_pk_add_f16, A2("v_pk_add_f16", ""))
 KERNEL(v_pk_max_f16, A2("v_pk_max_f16", ""))
+KERNEL(v_pk_maximum3_f16, A3("v_pk_maximum3_f16", ""))   /* gfx950: three-input IEEE maximum of both halves */
 /* ---- DPP / SDWA ---- */
 KERNEL(v_mov_dpp_wave_shr1, A1("v_mov_b32_dpp", " wave_shr:1 row_mask:0xf bank_mask:0xf"))
 KERNEL(v_mov_dpp_row_shr1, A1("v_mov_b32_dpp", " row_shr:1 row_mask:0xf bank_mask:0xf"))
@@ -120,6 +121,10 @@ KERNEL(v_add_u32_dpp_row_shr1, A2("v_add_u32_dpp", " row_shr:1 row_mask:0xf bank
 KERNEL(v_add_u32_sdwa, A2("v_add_u32_sdwa", " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1"))
 /* ---- mixes ---- */
 KERNEL(mix_pkadd_pkmax, AM("v_pk_add_i16", "v_pk_max_i16"))
+/* the two-operand op alternating with a three-operand one (4 + 4) */
+#define AM3(OPA, OPB)                                                                                                      \
+	OPA " %0, %0, %8\n" OPB " %1, %1, %8, %9\n" OPA " %2, %2, %8\n" OPB " %3, %3, %8, %9\n" OPA " %4, %4, %8\n" OPB " %5, %5, %8, %9\n" OPA " %6, %6, %8\n" OPB " %7, %7, %8, %9\n"
+KERNEL(mix_pkadd_pkmaximum3, AM3("v_pk_add_i16", "v_pk_maximum3_f16"))
 KERNEL(mix_pkmax_or, AM("v_pk_max_i16", "v_or_b32"))
 KERNEL(mix_pkmax_addu32, AM("v_pk_max_i16", "v_add_u32"))
 KERNEL(mix_7pkmax_1or, A71("v_pk_max_i16", "v_or_b32"))
@@ -145,9 +150,9 @@ static const Entry table[] = {
 	E(v_max3_i32), E(v_med3_i32), E(v_and_or_b32), E(v_or3_b32), E(v_bfi_b32), E(v_perm_b32), E(v_alignbit_b32), E(v_lshl_or_b32),
 	E(v_lshl_add_u32), E(v_add3_u32), E(v_xad_u32), E(v_fma_f32), E(v_max3_f32), E(v_max3_i16), E(v_mad_i32_i24), E(v_bfe_u32), E(v_bitop3_b32),
 	E(v_pk_add_i16), E(v_pk_add_i16_clamp), E(v_pk_sub_i16_clamp), E(v_pk_max_i16), E(v_pk_min_u16), E(v_pk_mad_i16),
-	E(v_pk_lshlrev_b16), E(v_pk_ashrrev_i16), E(v_pk_add_f16), E(v_pk_max_f16),
+	E(v_pk_lshlrev_b16), E(v_pk_ashrrev_i16), E(v_pk_add_f16), E(v_pk_max_f16), E(v_pk_maximum3_f16),
 	E(v_mov_dpp_wave_shr1), E(v_mov_dpp_row_shr1), E(v_mov_dpp_row_shl1), E(v_add_u32_dpp_row_shr1), E(v_add_u32_sdwa),
-	E(mix_pkadd_pkmax), E(mix_pkmax_or), E(mix_pkmax_addu32), E(mix_7pkmax_1or), E(mix_addu32_maxi32), E(mix_addf32_maxf32), E(mix_sdwaadd_max3), E(mix_bitop3_alignbit),
+	E(mix_pkadd_pkmax), E(mix_pkadd_pkmaximum3), E(mix_pkmax_or), E(mix_pkmax_addu32), E(mix_7pkmax_1or), E(mix_addu32_maxi32), E(mix_addf32_maxf32), E(mix_sdwaadd_max3), E(mix_bitop3_alignbit),
 };
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
