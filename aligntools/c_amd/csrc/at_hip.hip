@@ -18,8 +18,7 @@
 #include "at_infix.hip.h"
 #include "at_scan.hip.h"
 #include "at_scanhits.hip.h"
-#include "at_localscan.hip.h"
-#include "at_fitscan.hip.h"
+#include "at_tilescan.hip.h"
 #include "at_pairhits.hip.h"
 #include "../../../include/aligntools_hip.h"
 
@@ -2999,23 +2998,112 @@ extern "C" int at_scan(at_handle *h,
 	});
 }
 
-/* ---- Smith-Waterman of reads against long targets (at_scan_local; at_localscan.hip.h) ---- */
-extern "C" int at_scan_local_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutoff, int32_t tile_cols, int m, int u, int o, int e,
-                                  int32_t *tile, int32_t *overlap, int64_t *ntiles, int64_t *nfull)
+/* ---- reads against long targets, cut into tiles: Smith-Waterman (at_scan_local) and end-to-end affine alignment
+ * (at_scan_fit, 3.18); at_tilescan.hip.h ---- */
+/* what the two scans do differently on the host (the kernels' side: at_tilescan.hip.h); their texts, which differ in the order of
+ * their fields, stand as literals where they are written, local's beside fit's */
+struct TileScanFamily {
+	const char *who;                 /* the entry's name */
+	int mode;                        /* AT_MODE_LOCAL / AT_MODE_FIT: the sweep of a tile and of a window, the family of the kernels */
+	int32_t default_tile;
+	bool by_length;                  /* the targets sorted by length, a block's targets those no shorter than its queries (search_lists) */
+	bool target_need_base;           /* an empty target is an error (fit: it is shorter than every query: no candidate, no error) */
+	int64_t (*overlap)(int32_t l1, int use_cutoff, int32_t cutoff, int m, int u, int o, int e);
+	int (*check_scoring)(at_handle *h);                          /* the entry's refusals of a scoring, in its order */
+	int (*check_query)(at_handle *h, int64_t q, int32_t len);
+	/* a tile is a pair of the batch entry: its exact-score bound (align_device), said with the tile's numbers */
+	int (*check_range)(at_handle *h, int32_t l1, int32_t tile, int64_t ov, int32_t maxt, long long maxabs);
+	int32_t (*window_len)(const at_handle *h, int32_t l1, int32_t l2, int32_t score, int32_t end_i, int32_t end_j);   /* target columns of a hit's window */
+};
+
+static const TileScanFamily kScanLocal = {
+	"at_scan_local", AT_MODE_LOCAL, at::kLocalScanDefaultTile, false, true,
+	at::localscan_overlap,
+	[](at_handle *h) -> int {
+		if (at::localscan_scoring_ok(h->m, h->o, h->e) != AT_OK)
+			return fail(h, AT_ERR_DOMAIN, "at_scan_local needs m >= 1, o <= -1 and e <= -1: m = %d, o = %d, e = %d", h->m, h->o, h->e);
+		return AT_OK;
+	},
+	[](at_handle *h, int64_t q, int32_t len) -> int {
+		if (at::localscan_query_ok(len, h->m, h->u) != AT_OK)
+			return fail(h, AT_ERR_DOMAIN, "at_scan_local: query %lld has %d bases: at most %d, and max(m, u) * length < 2^%d", (long long)q, len,
+			            at::kLocalScanMaxQuery, at::kLocalScanScoreBits);
+		return AT_OK;
+	},
+	[](at_handle *h, int32_t l1, int32_t tile, int64_t ov, int32_t, long long maxabs) -> int {
+		if (maxabs * ((long long)l1 + tile + ov + 2) >= (1LL << 24))
+			return fail(h, AT_ERR_RANGE, "at_scan_local: a tile of %d rows x %d + %lld columns may leave the exact score range: max|param| = %lld", l1,
+			            tile, (long long)ov, maxabs);
+		return AT_OK;
+	},
+	[](const at_handle *h, int32_t, int32_t, int32_t score, int32_t end_i, int32_t end_j) -> int32_t {
+		return (int32_t)(end_j - at::localscan_window_start(end_j, end_i, score, h->m, h->u, h->o, h->e));
+	},
+};
+
+static const TileScanFamily kScanFit = {
+	"at_scan_fit", AT_MODE_FIT, at::kFitScanDefaultTile, true, false,
+	at::fitscan_overlap,
+	[](at_handle *h) -> int {
+		if (at::fitscan_scoring_ok(h->m, h->o, h->e) != AT_OK)
+			return fail(h, AT_ERR_DOMAIN, "at_scan_fit needs m >= 1, o <= -1 and e <= -1: m = %d, o = %d, e = %d", h->m, h->o, h->e);
+		if (h->use_jump) return fail(h, AT_ERR_DOMAIN, "at_scan_fit: jump sites (fit -s) are per-target columns and are not scanned: use_jump is set");
+		return AT_OK;
+	},
+	[](at_handle *h, int64_t q, int32_t len) -> int {
+		if (at::fitscan_query_ok(len) != AT_OK)
+			return fail(h, AT_ERR_DOMAIN, "at_scan_fit: query %lld has %d bases: at most %d", (long long)q, len, at::kFitScanMaxQuery);
+		return AT_OK;
+	},
+	[](at_handle *h, int32_t l1, int32_t tile, int64_t ov, int32_t maxt, long long maxabs) -> int {
+		const int64_t full_len = std::min<int64_t>(maxt, tile + ov);   /* the longest tile of the block */
+		if (maxabs * ((long long)l1 + full_len + 2) >= (1LL << 24))
+			return fail(h, AT_ERR_RANGE, "at_scan_fit: a tile of %d rows x %lld columns (tile = %d, overlap = %lld) may leave the exact score range: max|param| = %lld",
+			            l1, (long long)full_len, tile, (long long)ov, maxabs);
+		return AT_OK;
+	},
+	[](const at_handle *h, int32_t l1, int32_t l2, int32_t score, int32_t, int32_t end_j) -> int32_t {
+		const int64_t ws = at::fitscan_window_start(end_j, l1, score, h->m, h->u, h->o, h->e);
+		return (int32_t)(at::fitscan_window_end(end_j, ws, l1, l2) - ws);
+	},
+};
+
+/* what at_scan_local_plan and at_scan_fit_plan make of their planner's answer */
+template <typename Plan>
+static int tilescan_plan_out(const TileScanFamily &F, int rc, const Plan &sp, int32_t tile_cols, int32_t *tile, int32_t *overlap, int64_t *ntiles, int64_t *nfull)
 {
-	at::LocalScanPlan sp;
-	const int rc = at::localscan_plan(len1, len2, use_cutoff, cutoff, tile_cols, m, u, o, e, &sp);
 	if (rc == AT_ERR_ARG)
-		return fail(nullptr, AT_ERR_ARG, "at_scan_local_plan: a negative length, or tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)",
-		            tile_cols, at::kLocalScanDefaultTile);
-	if (rc != AT_OK)
-		return fail(nullptr, AT_ERR_DOMAIN, "at_scan_local_plan: needs m >= 1, o <= -1, e <= -1 and a query of 1 .. %d bases with max(m, u) * length < 2^%d",
-		            at::kLocalScanMaxQuery, at::kLocalScanScoreBits);
+		return fail(nullptr, AT_ERR_ARG, "%s_plan: a negative length, or tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)", F.who,
+		            tile_cols, F.default_tile);
+	if (rc != AT_OK) {
+		if (F.mode == AT_MODE_FIT)
+			return fail(nullptr, AT_ERR_DOMAIN, "at_scan_fit_plan: needs m >= 1, o <= -1, e <= -1, a query of 1 .. %d bases and a tile + overlap below 2^31",
+			            at::kFitScanMaxQuery);
+		else
+			return fail(nullptr, AT_ERR_DOMAIN, "at_scan_local_plan: needs m >= 1, o <= -1, e <= -1 and a query of 1 .. %d bases with max(m, u) * length < 2^%d",
+			            at::kLocalScanMaxQuery, at::kLocalScanScoreBits);
+	}
 	if (tile) *tile = sp.tile;
 	if (overlap) *overlap = sp.overlap;
 	if (ntiles) *ntiles = sp.ntiles;
 	if (nfull) *nfull = sp.nfull;
 	return AT_OK;
+}
+
+extern "C" int at_scan_local_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutoff, int32_t tile_cols, int m, int u, int o, int e,
+                                  int32_t *tile, int32_t *overlap, int64_t *ntiles, int64_t *nfull)
+{
+	at::LocalScanPlan sp;
+	const int rc = at::localscan_plan(len1, len2, use_cutoff, cutoff, tile_cols, m, u, o, e, &sp);
+	return tilescan_plan_out(kScanLocal, rc, sp, tile_cols, tile, overlap, ntiles, nfull);
+}
+
+extern "C" int at_scan_fit_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutoff, int32_t tile_cols, int m, int u, int o, int e,
+                                int32_t *tile, int32_t *overlap, int64_t *ntiles, int64_t *nfull)
+{
+	at::FitScanPlan sp;
+	const int rc = at::fitscan_plan(len1, len2, use_cutoff, cutoff, tile_cols, m, u, o, e, &sp);
+	return tilescan_plan_out(kScanFit, rc, sp, tile_cols, tile, overlap, ntiles, nfull);
 }
 
 extern "C" int64_t at_scan_local_window(int32_t end_i, int64_t end_j, int32_t score, int m, int u, int o, int e)
@@ -3024,23 +3112,45 @@ extern "C" int64_t at_scan_local_window(int32_t end_i, int64_t end_j, int32_t sc
 	return at::localscan_window_start(end_j, end_i, score, m, u, o, e);
 }
 
-/* the lists of at_scan_local: the blocks of search_lists with the targets in caller order.  A block's pairs go in RUNS of at most
- * `chunk` pairs whose key slots stay until every tile of the run is folded; a run's tiles go in two passes (the tiles of the full
- * shape, a uniform batch, and the shorter ones at the targets' ends) and each pass in SLICES of at most `chunk` tile pairs:
- * descriptors, the batch entry's sweep, fold.  Behind the last slice the run's slots are unpacked and merged.  The lists stay in
- * h->d_str behind the call. */
-static int localscan_lists(at_handle *h, const QuerySets &qt, const ReadSet &rs, int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile,
-                           const ListOut &out, ListBufs &lb)
+extern "C" int at_scan_fit_window(int64_t end_j, int32_t score, int32_t len1, int32_t len2, int m, int u, int o, int e, int64_t *ws, int64_t *we)
+{
+	if (at::fitscan_scoring_ok(m, o, e) != AT_OK || at::fitscan_query_ok(len1) != AT_OK)
+		return fail(nullptr, AT_ERR_DOMAIN, "at_scan_fit_window: needs m >= 1, o <= -1, e <= -1 and a query of 1 .. %d bases", at::kFitScanMaxQuery);
+	if (len2 < len1 || end_j < 0 || end_j >= len2)
+		return fail(nullptr, AT_ERR_ARG, "at_scan_fit_window: no hit of a %d x %d pair ends in column %lld", len1, len2, (long long)end_j);
+	const int64_t s = at::fitscan_window_start(end_j, len1, score, m, u, o, e);
+	if (ws) *ws = s;
+	if (we) *we = at::fitscan_window_end(end_j, s, len1, len2);
+	return AT_OK;
+}
+
+/* the lists of a tiled scan: the blocks of search_lists, for local with the targets in caller order and every block against all of
+ * them, for fit with the targets sorted by length and a block's targets those no shorter than its queries.  A block's pairs go in
+ * RUNS of at most `chunk` pairs whose key slots stay until every tile of the run is folded; a run's tiles go in two passes (the
+ * tiles of the full shape, a uniform batch, and the shorter ones at the targets' ends) and each pass in SLICES of at most `chunk`
+ * tile pairs: descriptors, the batch entry's sweep, fold.  Behind the last slice the run's slots are unpacked and merged.  The lists
+ * stay in h->d_str behind the call. */
+static int tilescan_lists(at_handle *h, const TileScanFamily &F, const QuerySets &qt, const ReadSet &rs, int k, int use_cutoff, int32_t cutoff, int strands,
+                          int32_t tile, const ListOut &out, ListBufs &lb)
 {
 	const int64_t nq = qt.nq, nt = qt.nt;
 	const int32_t *t_len = qt.t_len;
 	const at::QueryOrder qo = at::query_order(nq, qt.q_len, strands);
 	std::vector<int> tperm((size_t)nt);
 	std::iota(tperm.begin(), tperm.end(), 0);
+	if (F.by_length) std::stable_sort(tperm.begin(), tperm.end(), [&](int a, int b) { return t_len[a] < t_len[b]; });
+	std::vector<int32_t> tls((size_t)nt);
+	for (int64_t t = 0; t < nt; ++t) tls[(size_t)t] = t_len[tperm[(size_t)t]];
+	struct Block { int qa, nqb, ta; int64_t ntb; int32_t l1; };
+	std::vector<Block> blocks;
 	int64_t most = 0;
-	for (const at::QueryBlock &B : qo.blocks) most = std::max<int64_t>(most, (int64_t)B.nqb * nt);
-	int32_t maxt = 0;
-	for (int64_t t = 0; t < nt; ++t) maxt = std::max(maxt, t_len[t]);
+	for (const at::QueryBlock &Q : qo.blocks) {
+		const int64_t ta = F.by_length ? std::lower_bound(tls.begin(), tls.end(), Q.l1) - tls.begin() : 0;
+		if (ta == nt) continue;                                   /* every target is shorter than these queries */
+		blocks.push_back({Q.qa, Q.nqb, (int)ta, nt - ta, Q.l1});
+		most = std::max<int64_t>(most, (int64_t)Q.nqb * (nt - ta));
+	}
+	const int32_t maxt = *std::max_element(tls.begin(), tls.end());
 	/* a slice holds tile pairs: a run has at least as many tiles as pairs; its bound is that of the largest block's tiles (an upper bound:
 	 * some are not swept) */
 	const int64_t chunk = at::slice_clamp(env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault), most * std::max<int64_t>(1, at::localscan_tiles(maxt, tile)));
@@ -3066,100 +3176,88 @@ static int localscan_lists(at_handle *h, const QuerySets &qt, const ReadSet &rs,
 	StreamEvents ev;
 	if ((rc = ev.create(h, 2))) return rc;
 	HIP_TRY(h, hipEventRecord(ev.e[0], s));
+	long long maxabs = 1;
+	for (int v : {h->m, h->u, h->o, h->e, h->j}) maxabs = std::max<long long>(maxabs, std::llabs((long long)v));
 	std::vector<long long> tpre[2];
-	for (auto &v : tpre) v.assign((size_t)nt + 1, 0);
-	for (const at::QueryBlock &B : qo.blocks) {
+	for (const Block &B : blocks) {
 		/* the overlap depends on the query length: the block's prefix arrays of full and of shorter tiles per target */
-		const int64_t ov = at::localscan_overlap(B.l1, use_cutoff, cutoff, h->m, h->u, h->o, h->e);
-		{
-			/* a tile is a pair of the batch entry: its exact-score bound (align_device), said here with the tile's numbers */
-			long long maxabs = 1;
-			for (int v : {h->m, h->u, h->o, h->e, h->j}) maxabs = std::max<long long>(maxabs, std::llabs((long long)v));
-			if (maxabs * ((long long)B.l1 + tile + ov + 2) >= (1LL << 24))
-				return fail(h, AT_ERR_RANGE, "at_scan_local: a tile of %d rows x %d + %lld columns may leave the exact score range: max|param| = %lld", B.l1,
-				            tile, (long long)ov, maxabs);
-		}
+		const int64_t ov = F.overlap(B.l1, use_cutoff, cutoff, h->m, h->u, h->o, h->e);
+		if ((rc = F.check_range(h, B.l1, tile, ov, maxt, maxabs))) return rc;
 		ov_most = std::max(ov_most, ov);
-		int32_t rag_most = 0;
-		for (int64_t t = 0; t < nt; ++t) {
-			/* (the swept tiles: the repeats of tile 0 are left out) */
-			const int64_t n = at::localscan_swept(t_len[t], tile, ov), nf = at::localscan_swept_full(t_len[t], tile, ov);
-			const int64_t d = at::localscan_dropped(t_len[t], tile, ov);
-			tpre[0][(size_t)t + 1] = tpre[0][(size_t)t] + nf;
-			tpre[1][(size_t)t + 1] = tpre[1][(size_t)t] + (n - nf);
-			for (int64_t k2 = nf; k2 < n; ++k2) {
-				const int64_t x = at::localscan_swept_tile(k2, d);
-				rag_most = std::max<int32_t>(rag_most, (int32_t)(at::localscan_tile_end(x, tile, ov, t_len[t]) - at::localscan_tile_start(x, tile, ov)));
-			}
-		}
-		tiles_all += (tpre[0][(size_t)nt] + tpre[1][(size_t)nt]) * B.nqb;
+		const at::BlockTiles bt = at::block_tiles(tls.data() + B.ta, B.ntb, tile, ov, tpre);
+		tiles_all += bt.tiles * B.nqb;
 		/* (the copies read the vectors when they run: the stream is drained before the next block rewrites them) */
-		for (int x = 0; x < 2; ++x) HIP_TRY(h, hipMemcpyAsync(d_tpre[x], tpre[x].data(), ((size_t)nt + 1) * 8, hipMemcpyHostToDevice, s));
+		for (int x = 0; x < 2; ++x) HIP_TRY(h, hipMemcpyAsync(d_tpre[x], tpre[x].data(), ((size_t)B.ntb + 1) * 8, hipMemcpyHostToDevice, s));
 		HIP_TRY(h, hipStreamSynchronize(s));
-		const int64_t bp = (int64_t)B.nqb * nt;
+		const int64_t bp = (int64_t)B.nqb * B.ntb;
 		for (int64_t p0 = 0; p0 < bp; p0 += chunk) {
 			const int64_t n = std::min(chunk, bp - p0);
-			at::LocalScanArgs sa;
+			at::TileScanArgs sa;
 			memset(&sa, 0, sizeof sa);
-			sa.cap = chunk; sa.p0 = p0; sa.npairs = n; sa.ntb = nt;
-			sa.qa = B.qa; sa.nq = (int)nq; sa.enc = qo.enc; sa.nrev0 = (int)(nq + nt); sa.bpw = rs.bits == 2 ? 16 : 4; sa.qperm = d_qperm;
+			sa.cap = chunk; sa.p0 = p0; sa.npairs = n; sa.ntb = B.ntb;
+			sa.qa = B.qa; sa.ta = B.ta; sa.nq = (int)nq; sa.enc = qo.enc; sa.nrev0 = (int)(nq + nt); sa.bpw = rs.bits == 2 ? 16 : 4;
+			sa.qperm = d_qperm; sa.tperm = d_tperm;
 			sa.swoff = (const long long *)rs.d_swoff; sa.slen = rs.d_len; sa.tile = tile; sa.overlap = ov;
 			sa.woff1 = (long long *)d_woff1; sa.woff2 = (long long *)d_woff2; sa.len1 = d_len1; sa.len2 = d_len2; sa.s0 = d_s0; sa.slot = d_slot;
-			sa.score = d_r[0]; sa.end_i = d_r[1]; sa.end_j = d_r[2];
+			sa.score = d_r[0]; sa.end_i = d_r[1]; sa.end_j = d_r[2]; sa.state = d_r[3];
 			sa.key = d_pkey; sa.bad = lb.bad;
 			sa.o_score = d_r[4]; sa.o_end_i = d_r[5]; sa.o_end_j = d_r[6]; sa.o_state = d_r[7];
-			HIP_TRY(h, at_localscan_init_launch(&sa, h->ncu, s));
+			HIP_TRY(h, at_tilescan_init_launch(&sa, h->ncu, s));
 			for (int pass = 0; pass < 2; ++pass) {
-				const long long tall = tpre[pass][(size_t)nt];
+				const long long tall = tpre[pass][(size_t)B.ntb];
 				if (tall == 0) continue;
-				auto items_before = [&](int64_t x) { return (long long)(x / nt) * tall + tpre[pass][(size_t)(x % nt)]; };
+				auto items_before = [&](int64_t x) { return (long long)(x / B.ntb) * tall + tpre[pass][(size_t)(x % B.ntb)]; };
 				const long long ya = items_before(p0), yb = items_before(p0 + n);
 				sa.ragged = pass; sa.tall = tall; sa.tpre = d_tpre[pass];
 				for (long long y = ya; y < yb; y += chunk) {
 					sa.y0 = y; sa.nitems = std::min<long long>(chunk, yb - y);
-					HIP_TRY(h, at_localscan_desc_launch(&sa, h->ncu, s));
+					HIP_TRY(h, at_tilescan_desc_launch(F.mode, &sa, h->ncu, s));
 					BatchReq r(h);
-					r.mode = AT_MODE_LOCAL; r.npairs = sa.nitems; r.d_seq = rs.d_words; r.bits = rs.bits; r.stream = s;
+					r.mode = F.mode; r.npairs = sa.nitems; r.d_seq = rs.d_words; r.bits = rs.bits; r.stream = s;
 					r.d_woff1 = d_woff1; r.d_len1 = d_len1; r.d_woff2 = d_woff2; r.d_len2 = d_len2;
-					r.max_len1 = B.l1; r.max_len2 = pass ? rag_most : (int32_t)(tile + ov);
+					r.max_len1 = B.l1; r.max_len2 = pass ? bt.rag_most : (int32_t)(tile + ov);
 					r.uniform_shape = pass ? 0 : 1;
 					r.d_score = d_r[0]; r.d_end_i = d_r[1]; r.d_end_j = d_r[2]; r.d_state = d_r[3];
 					rc = align_device(h, r);
 					if (rc) { (void)hipStreamSynchronize(s); return rc; }
 					if (nslices == 0) cfg0 = h->cfg;
-					HIP_TRY(h, at_localscan_fold_launch(&sa, h->ncu, s));
+					HIP_TRY(h, at_tilescan_fold_launch(F.mode, &sa, h->ncu, s));
 					++nslices;
 				}
 			}
-			HIP_TRY(h, at_localscan_unpack_launch(&sa, h->ncu, s));
-			if ((rc = merge_slice(h, qo, lb, d_qperm, d_tperm, d_r + 4, p0, n, nt, B.qa, 0, k, 0, use_cutoff, cutoff))) return rc;
+			HIP_TRY(h, at_tilescan_unpack_launch(F.mode, &sa, h->ncu, s));
+			if ((rc = merge_slice(h, qo, lb, d_qperm, d_tperm, d_r + 4, p0, n, B.ntb, B.qa, B.ta, k, 0, use_cutoff, cutoff))) return rc;
 		}
 	}
 	HIP_TRY(h, hipEventRecord(ev.e[1], s));
-	if ((rc = lists_readback(h, lb, nq, k, qo.enc, false, "at_scan_local", out))) return rc;
+	if ((rc = lists_readback(h, lb, nq, k, qo.enc, false, F.who, out))) return rc;
 	float sweep_ms = 0.f;
 	HIP_TRY(h, hipEventElapsedTime(&sweep_ms, ev.e[0], ev.e[1]));
-	/* (the sweep phase's device time as scan_lists reports it: tools/local_scan_rate.py; at most 360 bytes, which localscan_cigars keeps whole) */
-	snprintf(h->cfg, sizeof h->cfg, "local-scan: tile=%d overlap<=%lld tiles=%lld k=%d strands=%s, %lld blocks, %lld slices; %.200s sweep=%.3fms", tile,
-	         (long long)ov_most, (long long)tiles_all, k, scan_strands_text(strands), (long long)qo.blocks.size(), (long long)nslices, cfg0.c_str(), (double)sweep_ms);
+	/* (the sweep phase's device time as scan_lists reports it: tools/local_scan_rate.py, tools/fit_scan_rate.py; at most 360 bytes, which
+	 * tilescan_cigars keeps whole) */
+	if (F.mode == AT_MODE_FIT)
+		snprintf(h->cfg, sizeof h->cfg, "scan-fit: tile=%d overlap=%lld tiles=%lld strands=%s, %lld blocks, %lld slices, k=%d; %.200s sweep=%.3fms", tile,
+		         (long long)ov_most, (long long)tiles_all, scan_strands_text(strands), (long long)blocks.size(), (long long)nslices, k, cfg0.c_str(), (double)sweep_ms);
+	else
+		snprintf(h->cfg, sizeof h->cfg, "local-scan: tile=%d overlap<=%lld tiles=%lld k=%d strands=%s, %lld blocks, %lld slices; %.200s sweep=%.3fms", tile,
+		         (long long)ov_most, (long long)tiles_all, k, scan_strands_text(strands), (long long)blocks.size(), (long long)nslices, cfg0.c_str(), (double)sweep_ms);
 	return AT_OK;
 }
 
-/* the alignments of the hits: every USED list entry as a window pair (query, target columns (ws, j*]) through the batch entry with
- * tracebacks and the CIGAR kernels (at_localscan.hip.h), in pieces of at most 2^20 hits or 1 GB of op slots (3.13's bounds) and no
- * more hits than a slice has pairs (AT_ALLPAIRS_CHUNK: the tests' 1 and 7 make pieces of 1 and 7 hits).  Unused entries keep what the entry gave them: 0 runs, a row of
- * -1 and no room in out_cigar */
-static int localscan_cigars(at_handle *h, int64_t nq, int k, int strands, const ReadSet &rs, int64_t nt, int32_t maxq, const ListBufs &lb,
-                            const int32_t *out_target, const int32_t *out_score, const int32_t *out_end_i, const int32_t *out_end_j, int flags,
-                            const CigarOut &co)
+/* the alignments of the hits: every USED list entry as a window pair (query, target columns of the hit's window) through the batch
+ * entry with tracebacks and the CIGAR kernels (at_tilescan.hip.h), in pieces of at most 2^20 hits or 1 GB of op slots (3.13's bounds)
+ * and no more hits than a slice has pairs (AT_ALLPAIRS_CHUNK: the tests' 1 and 7 make pieces of 1 and 7 hits).  Unused entries keep
+ * what the entry gave them: 0 runs, a row of -1 and no room in out_cigar */
+static int tilescan_cigars(at_handle *h, const TileScanFamily &F, const QuerySets &qt, int k, int strands, const ReadSet &rs, int32_t maxq, const ListBufs &lb,
+                           const ListOut &out, int flags, const CigarOut &co)
 {
-	const int64_t nlist = nq * k;
+	const int64_t nq = qt.nq, nt = qt.nt, nlist = nq * k;
 	std::vector<long long> used;
 	std::vector<int32_t> wlen;
 	for (int64_t e = 0; e < nlist; ++e) {
-		if (out_target[e] < 0) continue;
+		if (out.target[e] < 0) continue;
 		used.push_back(e);
-		wlen.push_back((int32_t)(out_end_j[e] - at::localscan_window_start(out_end_j[e], out_end_i[e], out_score[e], h->m, h->u, h->o, h->e)));
+		wlen.push_back(F.window_len(h, qt.q_len[e / k], qt.t_len[out.target[e]], out.score[e], out.end_i[e], out.end_j[e]));
 	}
 	const int64_t nused = (int64_t)used.size();
 	const int64_t piece_hits = std::max<long long>(1, std::min<long long>(env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault), 1LL << 20)), piece_ops = 1LL << 30;
@@ -3180,7 +3278,10 @@ static int localscan_cigars(at_handle *h, int64_t nq, int k, int strands, const 
 		}
 		const int64_t dcap = std::min<int64_t>(std::max<int64_t>(co.cap - words_total, 0), ops_bytes);   /* (a list has no more runs than ops) */
 		char bad_text[256];
-		snprintf(bad_text, sizeof bad_text, "at_scan_local: a hit's window does not reproduce its score and end cell (target columns (ws, j*] of at most %d)", max2);
+		if (F.mode == AT_MODE_FIT)
+			snprintf(bad_text, sizeof bad_text, "at_scan_fit: a hit's window does not reproduce its score, state and end column (target columns (ws, we] of at most %d)", max2);
+		else
+			snprintf(bad_text, sizeof bad_text, "at_scan_local: a hit's window does not reproduce its score and end cell (target columns (ws, j*] of at most %d)", max2);
 		std::vector<int32_t> hnc((size_t)n), hst((size_t)n * 8);
 		std::vector<int64_t> hco((size_t)n + 1);
 		WindowBufs w;
@@ -3189,22 +3290,22 @@ static int localscan_cigars(at_handle *h, int64_t nq, int k, int strands, const 
 		HIP_TRY(h, hipMemcpyAsync(w.ops_off, slot.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
 		HIP_TRY(h, hipMemcpyAsync(w.eidx, used.data() + a0, (size_t)n * 8, hipMemcpyHostToDevice, s));
 		HIP_TRY(h, hipMemsetAsync(w.bad, 0, 4, s));
-		at::LocalScanWindowArgs wa;
+		at::TileScanWindowArgs wa;
 		memset(&wa, 0, sizeof wa);
 		wa.n = n; wa.nlist = nlist; wa.eidx = w.eidx; wa.k = k; wa.nq = (int)nq; wa.enc = strands != AT_STRAND_FWD; wa.nrev0 = (int)(nq + nt);
 		wa.bpw = rs.bits == 2 ? 16 : 4;
 		wa.m = h->m; wa.u = h->u; wa.o = h->o; wa.e = h->e;
-		wa.lkey = lb.key; wa.lei = lb.ei; wa.lej = lb.ej;
+		wa.lkey = lb.key; wa.lei = lb.ei; wa.lej = lb.ej; wa.lst = lb.st;
 		wa.swoff = (const long long *)rs.d_swoff; wa.slen = rs.d_len;
 		wa.woff1 = (long long *)w.woff1; wa.woff2 = (long long *)w.woff2; wa.len1 = w.len1; wa.len2 = w.len2; wa.ws = w.aux;
-		wa.w_score = w.sc; wa.w_end_i = w.ei; wa.w_end_j = w.ej; wa.ncigar = w.ncigar; wa.stats = w.stats; wa.bad = w.bad;
-		HIP_TRY(h, at_localscan_window_launch(&wa, h->ncu, s));
-		rc = align_device(h, window_req(h, AT_MODE_LOCAL, n, rs, w, maxq, max2, s));
+		wa.w_score = w.sc; wa.w_end_i = w.ei; wa.w_end_j = w.ej; wa.w_state = w.st; wa.ncigar = w.ncigar; wa.stats = w.stats; wa.bad = w.bad;
+		HIP_TRY(h, at_tilescan_window_launch(F.mode, &wa, h->ncu, s));
+		rc = align_device(h, window_req(h, F.mode, n, rs, w, maxq, max2, s));
 		if (rc) { (void)hipStreamSynchronize(s); return rc; }
 		if (cfg1.empty()) cfg1 = h->cfg;
 		rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, w.woff1, w.woff2, w.ei, w.ej, w.ops, w.ops_off, w.nops, flags, w.ncigar, w.stats, w.coff, w.cigar, dcap, s);
 		if (rc) { (void)hipStreamSynchronize(s); return rc; }
-		HIP_TRY(h, at_localscan_check_launch(&wa, h->ncu, s));
+		HIP_TRY(h, at_tilescan_check_launch(F.mode, &wa, h->ncu, s));
 		if ((rc = window_fetch(h, w, n, bad_text, hnc.data(), hst.data(), hco.data()))) return rc;
 		for (int64_t x = 0; x < n; ++x) {
 			const int64_t e = used[(size_t)(a0 + x)];
@@ -3223,6 +3324,44 @@ static int localscan_cigars(at_handle *h, int64_t nq, int k, int strands, const 
 	for (; next_entry <= nlist; ++next_entry) co.off[next_entry] = words_total;
 	snprintf(h->cfg, sizeof h->cfg, "%.360s; windows: %.180s, %lld pieces, cigars: %d lanes/pair", cfg0.c_str(), cfg1.c_str(), (long long)npieces, h->last_cigar_lanes);
 	return AT_OK;
+}
+
+/* the body of at_scan_local and at_scan_fit: the shared refusals with the family's own in between, in the order each entry always had */
+static int tilescan_entry(at_handle *h, const TileScanFamily &F, const QuerySets &qt, int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile_cols,
+                          int flags, const ListOut &out, const CigarOut &co)
+{
+	const char *who = F.who;
+	if (!h) return fail(nullptr, AT_ERR_ARG, "%s: NULL handle", who);
+	const int64_t nq = qt.nq, nt = qt.nt;
+	int rc = check_sizes(h, who, nq, nt, co.cap, k);
+	if (rc || (rc = check_options(h, who, strands, tile_cols, F.default_tile, flags, co, nq, nt)) || (rc = check_one_gpu(h, who))) return rc;
+	const bool rev = strands != AT_STRAND_FWD;
+	if ((rc = F.check_scoring(h))) return rc;
+	if (nq == 0) return AT_OK;
+	if ((rc = check_list_pointers(h, who, qt, out, rev))) return rc;
+	int32_t maxq = 0;
+	for (int64_t q = 0; q < nq; ++q) {
+		if ((rc = check_read(h, "query", q, qt.q_len[q], qt.q_off[q], true)) || (rc = F.check_query(h, q, qt.q_len[q]))) return rc;
+		maxq = std::max(maxq, qt.q_len[q]);
+	}
+	for (int64_t t = 0; t < nt; ++t) if ((rc = check_read(h, "target", t, qt.t_len[t], qt.t_off[t], F.target_need_base))) return rc;
+	const int32_t tile = tile_cols > 0 ? tile_cols : F.default_tile;
+	return guarded(h, who, [&]() -> int {
+		list_out_init(out, nq, k, co);
+		if (nt == 0) {
+			if (F.mode == AT_MODE_FIT)
+				snprintf(h->cfg, sizeof h->cfg, "scan-fit: tile=%d overlap=0 tiles=0 strands=%s, 0 blocks, 0 slices, k=%d; ", tile, scan_strands_text(strands), k);
+			else
+				snprintf(h->cfg, sizeof h->cfg, "local-scan: tile=%d overlap<=0 tiles=0 k=%d strands=%s, 0 blocks, 0 slices; ", tile, k, scan_strands_text(strands));
+			return (int)AT_OK;
+		}
+		ReadSet rs;
+		int rc2 = upload_sets(h, F.mode, qt, rev, &rs);
+		if (rc2) return rc2;
+		ListBufs lb;
+		if ((rc2 = tilescan_lists(h, F, qt, rs, k, use_cutoff, cutoff, strands, tile, out, lb)) || !co.any()) return rc2;
+		return tilescan_cigars(h, F, qt, k, strands, rs, maxq, lb, out, flags, co);
+	});
 }
 
 extern "C" int at_scan_local(at_handle *h,
@@ -3234,288 +3373,9 @@ extern "C" int at_scan_local(at_handle *h,
                              int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
                              uint32_t *out_cigar, int64_t cigar_cap)
 {
-	const char *who = "at_scan_local";
-	if (!h) return fail(nullptr, AT_ERR_ARG, "at_scan_local: NULL handle");
-	const QuerySets qt = {nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len};
-	const ListOut out = {out_target, out_score, out_end_i, out_end_j, out_state, out_strand, out_nhits};
-	const CigarOut co = {out_stats, out_ncigar, out_cigar_off, out_cigar, cigar_cap};
-	int rc = check_sizes(h, who, nq, nt, cigar_cap, k);
-	if (rc || (rc = check_options(h, who, strands, tile_cols, at::kLocalScanDefaultTile, flags, co, nq, nt)) || (rc = check_one_gpu(h, who))) return rc;
-	const bool rev = strands != AT_STRAND_FWD;
-	if (at::localscan_scoring_ok(h->m, h->o, h->e) != AT_OK)
-		return fail(h, AT_ERR_DOMAIN, "at_scan_local needs m >= 1, o <= -1 and e <= -1: m = %d, o = %d, e = %d", h->m, h->o, h->e);
-	if (nq == 0) return AT_OK;
-	if ((rc = check_list_pointers(h, who, qt, out, rev))) return rc;
-	int32_t maxq = 0;
-	for (int64_t q = 0; q < nq; ++q) {
-		if ((rc = check_read(h, "query", q, q_len[q], q_off[q], true))) return rc;
-		if (at::localscan_query_ok(q_len[q], h->m, h->u) != AT_OK)
-			return fail(h, AT_ERR_DOMAIN, "at_scan_local: query %lld has %d bases: at most %d, and max(m, u) * length < 2^%d", (long long)q, q_len[q],
-			            at::kLocalScanMaxQuery, at::kLocalScanScoreBits);
-		maxq = std::max(maxq, q_len[q]);
-	}
-	for (int64_t t = 0; t < nt; ++t) if ((rc = check_read(h, "target", t, t_len[t], t_off[t], true))) return rc;
-	const int32_t tile = tile_cols > 0 ? tile_cols : at::kLocalScanDefaultTile;
-	return guarded(h, who, [&]() -> int {
-		list_out_init(out, nq, k, co);
-		if (nt == 0) {
-			snprintf(h->cfg, sizeof h->cfg, "local-scan: tile=%d overlap<=0 tiles=0 k=%d strands=%s, 0 blocks, 0 slices; ", tile, k, scan_strands_text(strands));
-			return (int)AT_OK;
-		}
-		ReadSet rs;
-		int rc2 = upload_sets(h, AT_MODE_LOCAL, qt, rev, &rs);
-		if (rc2) return rc2;
-		ListBufs lb;
-		if ((rc2 = localscan_lists(h, qt, rs, k, use_cutoff, cutoff, strands, tile, out, lb)) || !co.any()) return rc2;
-		return localscan_cigars(h, nq, k, strands, rs, nt, maxq, lb, out_target, out_score, out_end_i, out_end_j, flags, co);
-	});
-}
-
-/* ---- end-to-end affine alignment of reads against long targets (at_scan_fit; at_fitscan.hip.h) ---- */
-extern "C" int at_scan_fit_plan(int32_t len1, int32_t len2, int use_cutoff, int32_t cutoff, int32_t tile_cols, int m, int u, int o, int e,
-                                int32_t *tile, int32_t *overlap, int64_t *ntiles, int64_t *nfull)
-{
-	at::FitScanPlan sp;
-	const int rc = at::fitscan_plan(len1, len2, use_cutoff, cutoff, tile_cols, m, u, o, e, &sp);
-	if (rc == AT_ERR_ARG)
-		return fail(nullptr, AT_ERR_ARG, "at_scan_fit_plan: a negative length, or tile_cols = %d is not a positive multiple of 16 (or 0 for the default, %d)",
-		            tile_cols, at::kFitScanDefaultTile);
-	if (rc != AT_OK)
-		return fail(nullptr, AT_ERR_DOMAIN, "at_scan_fit_plan: needs m >= 1, o <= -1, e <= -1, a query of 1 .. %d bases and a tile + overlap below 2^31",
-		            at::kFitScanMaxQuery);
-	if (tile) *tile = sp.tile;
-	if (overlap) *overlap = sp.overlap;
-	if (ntiles) *ntiles = sp.ntiles;
-	if (nfull) *nfull = sp.nfull;
-	return AT_OK;
-}
-
-extern "C" int at_scan_fit_window(int64_t end_j, int32_t score, int32_t len1, int32_t len2, int m, int u, int o, int e, int64_t *ws, int64_t *we)
-{
-	if (at::fitscan_scoring_ok(m, o, e) != AT_OK || at::fitscan_query_ok(len1) != AT_OK)
-		return fail(nullptr, AT_ERR_DOMAIN, "at_scan_fit_window: needs m >= 1, o <= -1, e <= -1 and a query of 1 .. %d bases", at::kFitScanMaxQuery);
-	if (len2 < len1 || end_j < 0 || end_j >= len2)
-		return fail(nullptr, AT_ERR_ARG, "at_scan_fit_window: no hit of a %d x %d pair ends in column %lld", len1, len2, (long long)end_j);
-	const int64_t s = at::fitscan_window_start(end_j, len1, score, m, u, o, e);
-	if (ws) *ws = s;
-	if (we) *we = at::fitscan_window_end(end_j, s, len1, len2);
-	return AT_OK;
-}
-
-/* the lists of at_scan_fit: the blocks of search_lists (the targets sorted by length, a block's targets those no shorter than its
- * queries) swept the way localscan_lists sweeps: a block's pairs in RUNS of at most `chunk` pairs whose key slots stay until every
- * tile of the run is folded, a run's tiles in two passes (the full shape, a uniform batch, and the shorter ones at the targets' ends),
- * each pass in SLICES of at most `chunk` tile pairs.  The lists stay in h->d_str behind the call. */
-static int fitscan_lists(at_handle *h, const QuerySets &qt, const ReadSet &rs, int k, int use_cutoff, int32_t cutoff, int strands, int32_t tile,
-                         const ListOut &out, ListBufs &lb)
-{
-	const int64_t nq = qt.nq, nt = qt.nt;
-	const int32_t *t_len = qt.t_len;
-	const at::QueryOrder qo = at::query_order(nq, qt.q_len, strands);
-	std::vector<int> tperm((size_t)nt);
-	std::iota(tperm.begin(), tperm.end(), 0);
-	std::stable_sort(tperm.begin(), tperm.end(), [&](int a, int b) { return t_len[a] < t_len[b]; });
-	std::vector<int32_t> tls((size_t)nt);
-	for (int64_t t = 0; t < nt; ++t) tls[(size_t)t] = t_len[tperm[(size_t)t]];
-	struct Block { int qa, nqb, ta; int64_t ntb; int32_t l1; };
-	std::vector<Block> blocks;
-	int64_t most = 0;
-	for (const at::QueryBlock &Q : qo.blocks) {
-		const int64_t ta = std::lower_bound(tls.begin(), tls.end(), Q.l1) - tls.begin();
-		if (ta == nt) continue;                                   /* every target is shorter than these queries */
-		blocks.push_back({Q.qa, Q.nqb, (int)ta, nt - ta, Q.l1});
-		most = std::max<int64_t>(most, (int64_t)Q.nqb * (nt - ta));
-	}
-	const int32_t maxt = tls.back();
-	/* (a slice holds tile pairs; its bound as in localscan_lists) */
-	const int64_t chunk = at::slice_clamp(env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault), most * std::max<int64_t>(1, at::localscan_tiles(maxt, tile)));
-	int64_t *d_woff1 = nullptr, *d_woff2 = nullptr; long long *d_s0 = nullptr, *d_slot = nullptr, *d_tpre[2]; unsigned long long *d_pkey = nullptr;
-	int32_t *d_len1 = nullptr, *d_len2 = nullptr, *d_r[8]; int *d_qperm = nullptr, *d_tperm = nullptr;
-	int rc = carve(h, &h->d_desc, &h->desc_bytes, [&](Carver &c) {
-		d_woff1 = c.take<int64_t>((size_t)chunk); d_woff2 = c.take<int64_t>((size_t)chunk);
-		d_s0 = c.take<long long>((size_t)chunk); d_slot = c.take<long long>((size_t)chunk);
-		d_pkey = c.take<unsigned long long>((size_t)chunk);
-		d_len1 = c.take<int32_t>((size_t)chunk); d_len2 = c.take<int32_t>((size_t)chunk);
-		for (long long *&x : d_tpre) x = c.take<long long>((size_t)nt + 1);
-		d_qperm = c.take<int>((size_t)qo.nv); d_tperm = c.take<int>((size_t)nt);
-	});
-	if (!rc) rc = carve(h, &h->d_out, &h->out_bytes, [&](Carver &c) { for (int32_t *&x : d_r) x = c.take<int32_t>((size_t)chunk); });
-	if (!rc) rc = list_bufs(h, (size_t)nq * (size_t)k, true, &lb);
-	if (rc) return rc;
-	hipStream_t s = h->stream;
-	HIP_TRY(h, hipMemcpyAsync(d_qperm, qo.qperm.data(), (size_t)qo.nv * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemcpyAsync(d_tperm, tperm.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(h, hipMemsetAsync(lb.key, 0, lb.lbytes, s));
-	std::string cfg0;
-	int64_t nslices = 0, tiles_all = 0, ov_most = 0;
-	StreamEvents ev;
-	if ((rc = ev.create(h, 2))) return rc;
-	HIP_TRY(h, hipEventRecord(ev.e[0], s));
-	std::vector<long long> tpre[2];
-	for (const Block &B : blocks) {
-		/* the overlap depends on the query length: the block's prefix arrays of full and of shorter tiles per target */
-		const int64_t ov = at::fitscan_overlap(B.l1, use_cutoff, cutoff, h->m, h->u, h->o, h->e);
-		const int64_t full_len = std::min<int64_t>(maxt, tile + ov);   /* the longest tile of the block */
-		{
-			/* a tile is a pair of the batch entry: its exact-score bound (align_device), said here with the tile's numbers */
-			long long maxabs = 1;
-			for (int v : {h->m, h->u, h->o, h->e, h->j}) maxabs = std::max<long long>(maxabs, std::llabs((long long)v));
-			if (maxabs * ((long long)B.l1 + full_len + 2) >= (1LL << 24))
-				return fail(h, AT_ERR_RANGE, "at_scan_fit: a tile of %d rows x %lld columns (tile = %d, overlap = %lld) may leave the exact score range: max|param| = %lld",
-				            B.l1, (long long)full_len, tile, (long long)ov, maxabs);
-		}
-		ov_most = std::max(ov_most, ov);
-		int32_t rag_most = 0;
-		for (auto &v : tpre) v.assign((size_t)B.ntb + 1, 0);
-		for (int64_t t = 0; t < B.ntb; ++t) {
-			const int32_t l2 = tls[(size_t)(B.ta + t)];
-			/* (the swept tiles: the repeats of tile 0 are left out) */
-			const int64_t n = at::fitscan_swept(B.l1, l2, tile, ov), nf = at::fitscan_swept_full(B.l1, l2, tile, ov);
-			const int64_t d = at::fitscan_dropped(B.l1, l2, tile, ov);
-			tpre[0][(size_t)t + 1] = tpre[0][(size_t)t] + nf;
-			tpre[1][(size_t)t + 1] = tpre[1][(size_t)t] + (n - nf);
-			for (int64_t k2 = nf; k2 < n; ++k2) {
-				const int64_t x = at::fitscan_swept_tile(k2, d);
-				rag_most = std::max<int32_t>(rag_most, (int32_t)(at::fitscan_tile_end(x, tile, ov, l2) - at::fitscan_tile_start(x, tile, ov)));
-			}
-		}
-		tiles_all += (tpre[0][(size_t)B.ntb] + tpre[1][(size_t)B.ntb]) * B.nqb;
-		/* (the copies read the vectors when they run: the stream is drained before the next block rewrites them) */
-		for (int x = 0; x < 2; ++x) HIP_TRY(h, hipMemcpyAsync(d_tpre[x], tpre[x].data(), ((size_t)B.ntb + 1) * 8, hipMemcpyHostToDevice, s));
-		HIP_TRY(h, hipStreamSynchronize(s));
-		const int64_t bp = (int64_t)B.nqb * B.ntb;
-		for (int64_t p0 = 0; p0 < bp; p0 += chunk) {
-			const int64_t n = std::min(chunk, bp - p0);
-			at::FitScanArgs sa;
-			memset(&sa, 0, sizeof sa);
-			sa.cap = chunk; sa.p0 = p0; sa.npairs = n; sa.ntb = B.ntb;
-			sa.qa = B.qa; sa.ta = B.ta; sa.nq = (int)nq; sa.enc = qo.enc; sa.nrev0 = (int)(nq + nt); sa.bpw = rs.bits == 2 ? 16 : 4;
-			sa.qperm = d_qperm; sa.tperm = d_tperm;
-			sa.swoff = (const long long *)rs.d_swoff; sa.slen = rs.d_len; sa.tile = tile; sa.overlap = ov;
-			sa.woff1 = (long long *)d_woff1; sa.woff2 = (long long *)d_woff2; sa.len1 = d_len1; sa.len2 = d_len2; sa.s0 = d_s0; sa.slot = d_slot;
-			sa.score = d_r[0]; sa.end_j = d_r[2]; sa.state = d_r[3];
-			sa.key = d_pkey; sa.bad = lb.bad;
-			sa.o_score = d_r[4]; sa.o_end_i = d_r[5]; sa.o_end_j = d_r[6]; sa.o_state = d_r[7];
-			{
-				at::LocalScanArgs ia;                             /* the slots start as all ones: the local scan's kernel, unchanged */
-				memset(&ia, 0, sizeof ia);
-				ia.cap = chunk; ia.npairs = n; ia.key = d_pkey;
-				HIP_TRY(h, at_localscan_init_launch(&ia, h->ncu, s));
-			}
-			for (int pass = 0; pass < 2; ++pass) {
-				const long long tall = tpre[pass][(size_t)B.ntb];
-				if (tall == 0) continue;
-				auto items_before = [&](int64_t x) { return (long long)(x / B.ntb) * tall + tpre[pass][(size_t)(x % B.ntb)]; };
-				const long long ya = items_before(p0), yb = items_before(p0 + n);
-				sa.ragged = pass; sa.tall = tall; sa.tpre = d_tpre[pass];
-				for (long long y = ya; y < yb; y += chunk) {
-					sa.y0 = y; sa.nitems = std::min<long long>(chunk, yb - y);
-					HIP_TRY(h, at_fitscan_desc_launch(&sa, h->ncu, s));
-					BatchReq r(h);
-					r.mode = AT_MODE_FIT; r.npairs = sa.nitems; r.d_seq = rs.d_words; r.bits = rs.bits; r.stream = s;
-					r.d_woff1 = d_woff1; r.d_len1 = d_len1; r.d_woff2 = d_woff2; r.d_len2 = d_len2;
-					r.max_len1 = B.l1; r.max_len2 = pass ? rag_most : (int32_t)(tile + ov);
-					r.uniform_shape = pass ? 0 : 1;
-					r.d_score = d_r[0]; r.d_end_i = d_r[1]; r.d_end_j = d_r[2]; r.d_state = d_r[3];
-					rc = align_device(h, r);
-					if (rc) { (void)hipStreamSynchronize(s); return rc; }
-					if (nslices == 0) cfg0 = h->cfg;
-					HIP_TRY(h, at_fitscan_fold_launch(&sa, h->ncu, s));
-					++nslices;
-				}
-			}
-			HIP_TRY(h, at_fitscan_unpack_launch(&sa, h->ncu, s));
-			if ((rc = merge_slice(h, qo, lb, d_qperm, d_tperm, d_r + 4, p0, n, B.ntb, B.qa, B.ta, k, 0, use_cutoff, cutoff))) return rc;
-		}
-	}
-	HIP_TRY(h, hipEventRecord(ev.e[1], s));
-	if ((rc = lists_readback(h, lb, nq, k, qo.enc, false, "at_scan_fit", out))) return rc;
-	float sweep_ms = 0.f;
-	HIP_TRY(h, hipEventElapsedTime(&sweep_ms, ev.e[0], ev.e[1]));
-	/* (the sweep phase's device time: tools/fit_scan_rate.py; at most 360 bytes, which fitscan_cigars keeps whole) */
-	snprintf(h->cfg, sizeof h->cfg, "scan-fit: tile=%d overlap=%lld tiles=%lld strands=%s, %lld blocks, %lld slices, k=%d; %.200s sweep=%.3fms", tile,
-	         (long long)ov_most, (long long)tiles_all, scan_strands_text(strands), (long long)blocks.size(), (long long)nslices, k, cfg0.c_str(), (double)sweep_ms);
-	return AT_OK;
-}
-
-/* the alignments of the hits: every USED list entry as a window pair (query, target columns (ws, we]) through the batch entry with
- * tracebacks and the CIGAR kernels (at_fitscan.hip.h), in the pieces of localscan_cigars.  Unused entries keep what the entry gave
- * them: 0 runs, a row of -1 and no room in out_cigar */
-static int fitscan_cigars(at_handle *h, const QuerySets &qt, int k, int strands, const ReadSet &rs, int32_t maxq, const ListBufs &lb,
-                          const int32_t *out_target, const int32_t *out_score, const int32_t *out_end_j, int flags, const CigarOut &co)
-{
-	const int64_t nq = qt.nq, nt = qt.nt, nlist = nq * k;
-	std::vector<long long> used;
-	std::vector<int32_t> wlen;
-	for (int64_t e = 0; e < nlist; ++e) {
-		if (out_target[e] < 0) continue;
-		const int32_t l1 = qt.q_len[e / k], l2 = qt.t_len[out_target[e]];
-		const int64_t ws = at::fitscan_window_start(out_end_j[e], l1, out_score[e], h->m, h->u, h->o, h->e);
-		used.push_back(e);
-		wlen.push_back((int32_t)(at::fitscan_window_end(out_end_j[e], ws, l1, l2) - ws));
-	}
-	const int64_t nused = (int64_t)used.size();
-	const int64_t piece_hits = std::max<long long>(1, std::min<long long>(env_ll("AT_ALLPAIRS_CHUNK", at::kSliceDefault), 1LL << 20)), piece_ops = 1LL << 30;
-	hipStream_t s = h->stream;
-	const std::string cfg0 = h->cfg;
-	std::string cfg1;
-	int64_t words_total = 0, npieces = 0;   /* CIGAR words of the hits so far: the next piece's place in out_cigar */
-	bool fits = true;                        /* every entry so far ends within the caller's capacity */
-	int64_t next_entry = 0;                  /* out_cigar_off is complete up to here */
-	for (int64_t a0 = 0; a0 < nused; ) {
-		int64_t ops_bytes = 0;
-		const int64_t n = at::piece_end(a0, nused, piece_hits, piece_ops, [&](int64_t x) { return (int64_t)maxq + wlen[(size_t)x]; }, &ops_bytes) - a0;
-		int32_t max2 = 1;
-		std::vector<int64_t> slot((size_t)n);
-		for (int64_t x = 0, at = 0; x < n; at += (int64_t)maxq + wlen[(size_t)(a0 + x)], ++x) {
-			slot[(size_t)x] = at;
-			max2 = std::max(max2, wlen[(size_t)(a0 + x)]);
-		}
-		const int64_t dcap = std::min<int64_t>(std::max<int64_t>(co.cap - words_total, 0), ops_bytes);   /* (a list has no more runs than ops) */
-		char bad_text[256];
-		snprintf(bad_text, sizeof bad_text, "at_scan_fit: a hit's window does not reproduce its score, state and end column (target columns (ws, we] of at most %d)", max2);
-		std::vector<int32_t> hnc((size_t)n), hst((size_t)n * 8);
-		std::vector<int64_t> hco((size_t)n + 1);
-		WindowBufs w;
-		int rc = window_carve(h, n, dcap, 0, true, false, &h->d_order, &h->order_bytes, (size_t)ops_bytes + 256, w);
-		if (rc) return rc;
-		HIP_TRY(h, hipMemcpyAsync(w.ops_off, slot.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-		HIP_TRY(h, hipMemcpyAsync(w.eidx, used.data() + a0, (size_t)n * 8, hipMemcpyHostToDevice, s));
-		HIP_TRY(h, hipMemsetAsync(w.bad, 0, 4, s));
-		at::FitScanWindowArgs wa;
-		memset(&wa, 0, sizeof wa);
-		wa.n = n; wa.nlist = nlist; wa.eidx = w.eidx; wa.k = k; wa.nq = (int)nq; wa.enc = strands != AT_STRAND_FWD; wa.nrev0 = (int)(nq + nt);
-		wa.bpw = rs.bits == 2 ? 16 : 4;
-		wa.m = h->m; wa.u = h->u; wa.o = h->o; wa.e = h->e;
-		wa.lkey = lb.key; wa.lej = lb.ej; wa.lst = lb.st;
-		wa.swoff = (const long long *)rs.d_swoff; wa.slen = rs.d_len;
-		wa.woff1 = (long long *)w.woff1; wa.woff2 = (long long *)w.woff2; wa.len1 = w.len1; wa.len2 = w.len2; wa.ws = w.aux;
-		wa.w_score = w.sc; wa.w_end_j = w.ej; wa.w_state = w.st; wa.ncigar = w.ncigar; wa.stats = w.stats; wa.bad = w.bad;
-		HIP_TRY(h, at_fitscan_window_launch(&wa, h->ncu, s));
-		rc = align_device(h, window_req(h, AT_MODE_FIT, n, rs, w, maxq, max2, s));
-		if (rc) { (void)hipStreamSynchronize(s); return rc; }
-		if (cfg1.empty()) cfg1 = h->cfg;
-		rc = at_cigar_batch_device(h, n, rs.d_words, rs.bits, w.woff1, w.woff2, w.ei, w.ej, w.ops, w.ops_off, w.nops, flags, w.ncigar, w.stats, w.coff, w.cigar, dcap, s);
-		if (rc) { (void)hipStreamSynchronize(s); return rc; }
-		HIP_TRY(h, at_fitscan_check_launch(&wa, h->ncu, s));
-		if ((rc = window_fetch(h, w, n, bad_text, hnc.data(), hst.data(), hco.data()))) return rc;
-		for (int64_t x = 0; x < n; ++x) {
-			const int64_t e = used[(size_t)(a0 + x)];
-			for (; next_entry <= e; ++next_entry) co.off[next_entry] = words_total + hco[(size_t)x];
-			co.ncigar[e] = hnc[(size_t)x];
-			memcpy(co.stats + e * 8, hst.data() + x * 8, 32);
-		}
-		/* the piece's words that end within the caller's capacity: a prefix of the device buffer, behind the pieces before it */
-		const int64_t room = fits ? co.cap - words_total : 0;
-		if ((rc = window_words(h, w, hco.data(), n, room, room > 0 ? co.words + words_total : nullptr))) return rc;
-		fits = fits && hco[(size_t)n] <= room;
-		words_total += hco[(size_t)n];
-		a0 += n;
-		++npieces;
-	}
-	for (; next_entry <= nlist; ++next_entry) co.off[next_entry] = words_total;
-	snprintf(h->cfg, sizeof h->cfg, "%.360s; windows: %.180s, %lld pieces, cigars: %d lanes/pair", cfg0.c_str(), cfg1.c_str(), (long long)npieces, h->last_cigar_lanes);
-	return AT_OK;
+	return tilescan_entry(h, kScanLocal, {nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len}, k, use_cutoff, cutoff, strands, tile_cols, flags,
+	                      {out_target, out_score, out_end_i, out_end_j, out_state, out_strand, out_nhits},
+	                      {out_stats, out_ncigar, out_cigar_off, out_cigar, cigar_cap});
 }
 
 extern "C" int at_scan_fit(at_handle *h,
@@ -3527,42 +3387,9 @@ extern "C" int at_scan_fit(at_handle *h,
                            int32_t *out_stats, int32_t *out_ncigar, int64_t *out_cigar_off,
                            uint32_t *out_cigar, int64_t cigar_cap)
 {
-	const char *who = "at_scan_fit";
-	if (!h) return fail(nullptr, AT_ERR_ARG, "at_scan_fit: NULL handle");
-	const QuerySets qt = {nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len};
-	const ListOut out = {out_target, out_score, out_end_i, out_end_j, out_state, out_strand, out_nhits};
-	const CigarOut co = {out_stats, out_ncigar, out_cigar_off, out_cigar, cigar_cap};
-	int rc = check_sizes(h, who, nq, nt, cigar_cap, k);
-	if (rc || (rc = check_options(h, who, strands, tile_cols, at::kFitScanDefaultTile, flags, co, nq, nt)) || (rc = check_one_gpu(h, who))) return rc;
-	const bool rev = strands != AT_STRAND_FWD;
-	if (at::fitscan_scoring_ok(h->m, h->o, h->e) != AT_OK)
-		return fail(h, AT_ERR_DOMAIN, "at_scan_fit needs m >= 1, o <= -1 and e <= -1: m = %d, o = %d, e = %d", h->m, h->o, h->e);
-	if (h->use_jump) return fail(h, AT_ERR_DOMAIN, "at_scan_fit: jump sites (fit -s) are per-target columns and are not scanned: use_jump is set");
-	if (nq == 0) return AT_OK;
-	if ((rc = check_list_pointers(h, who, qt, out, rev))) return rc;
-	int32_t maxq = 0;
-	for (int64_t q = 0; q < nq; ++q) {
-		if ((rc = check_read(h, "query", q, q_len[q], q_off[q], true))) return rc;
-		if (at::fitscan_query_ok(q_len[q]) != AT_OK)
-			return fail(h, AT_ERR_DOMAIN, "at_scan_fit: query %lld has %d bases: at most %d", (long long)q, q_len[q], at::kFitScanMaxQuery);
-		maxq = std::max(maxq, q_len[q]);
-	}
-	/* (an empty target is shorter than every query: no candidate, no error) */
-	for (int64_t t = 0; t < nt; ++t) if ((rc = check_read(h, "target", t, t_len[t], t_off[t], false))) return rc;
-	const int32_t tile = tile_cols > 0 ? tile_cols : at::kFitScanDefaultTile;
-	return guarded(h, who, [&]() -> int {
-		list_out_init(out, nq, k, co);
-		if (nt == 0) {
-			snprintf(h->cfg, sizeof h->cfg, "scan-fit: tile=%d overlap=0 tiles=0 strands=%s, 0 blocks, 0 slices, k=%d; ", tile, scan_strands_text(strands), k);
-			return (int)AT_OK;
-		}
-		ReadSet rs;
-		int rc2 = upload_sets(h, AT_MODE_FIT, qt, rev, &rs);
-		if (rc2) return rc2;
-		ListBufs lb;
-		if ((rc2 = fitscan_lists(h, qt, rs, k, use_cutoff, cutoff, strands, tile, out, lb)) || !co.any()) return rc2;
-		return fitscan_cigars(h, qt, k, strands, rs, maxq, lb, out_target, out_score, out_end_j, flags, co);
-	});
+	return tilescan_entry(h, kScanFit, {nq, q_blob, q_off, q_len, nt, t_blob, t_off, t_len}, k, use_cutoff, cutoff, strands, tile_cols, flags,
+	                      {out_target, out_score, out_end_i, out_end_j, out_state, out_strand, out_nhits},
+	                      {out_stats, out_ncigar, out_cigar_off, out_cigar, cigar_cap});
 }
 
 /* ---- every occurrence of a read under a distance cutoff (at_scan_hits; at_scanhits.hip.h) ---- */

@@ -1,8 +1,8 @@
 /*
- * at_queryplan.h -- the host arithmetic that the query-vs-target entries share (at_search, at_scan, at_scan_local, at_scan_hits,
- * at_allpairs_hits): the order in which the queries are swept and its blocks of one length, the bound of a slice,
- * the 64-bit key of a list entry, the pieces of a window pass and the CIGAR words that fit the caller's array.  Pure arithmetic:
- * plain C++17, no HIP.
+ * at_queryplan.h -- the host arithmetic that the query-vs-target entries share (at_search, at_scan, at_scan_local, at_scan_fit,
+ * at_scan_hits, at_allpairs_hits): the order in which the queries are swept and its blocks of one length, the bound
+ * of a slice, the 64-bit key of a list entry, the pieces of a window pass, the CIGAR words that fit the caller's array and the tiles
+ * of a block of the tiled scans.  Pure arithmetic: plain C++17, no HIP.
  *
  * The queries are swept in the stable order of their lengths.  With a reverse strand an entry of that order is (query << 1) | strand
  * (at_search.hip.h); with both strands a query's two entries are adjacent, strand 0 first: same length, same block, one run of
@@ -16,6 +16,8 @@
 #include <algorithm>
 #include <cstdint>
 #include <vector>
+
+#include "at_localscan_plan.h"
 
 namespace at {
 
@@ -93,6 +95,34 @@ inline int64_t prefix_fit(const int64_t *off, int64_t n, int64_t cap)
 	int64_t fit = 0;
 	for (int64_t e = 0; e < n && off[e + 1] <= cap; ++e) fit = off[e + 1];
 	return fit;
+}
+
+/* The tiles of one block of a tiled scan (at_scan_local, at_scan_fit; at_localscan_plan.h has the cut, which is fit's too for targets
+ * no shorter than the query -- a fit block has no others): the targets t_len[0 .. ntb), tiles of `tile` own columns and `ov` in front.
+ * tpre[0] / tpre[1], [ntb + 1]: the swept tiles of the full shape (tile + ov columns) / the shorter ones at the targets' ends, of the
+ * targets in front of target t. */
+struct BlockTiles {
+	int64_t tiles;       /* swept tiles of all targets, both passes */
+	int32_t rag_most;    /* columns of the longest tile of the second pass; 0 without one */
+};
+
+inline BlockTiles block_tiles(const int32_t *t_len, int64_t ntb, int32_t tile, int64_t ov, std::vector<long long> tpre[2])
+{
+	BlockTiles b = {0, 0};
+	for (int x = 0; x < 2; ++x) tpre[x].assign((size_t)ntb + 1, 0);
+	for (int64_t t = 0; t < ntb; ++t) {
+		const int32_t l2 = t_len[t];
+		/* (the swept tiles: the repeats of tile 0 are left out) */
+		const int64_t n = localscan_swept(l2, tile, ov), nf = localscan_swept_full(l2, tile, ov), d = localscan_dropped(l2, tile, ov);
+		tpre[0][(size_t)t + 1] = tpre[0][(size_t)t] + nf;
+		tpre[1][(size_t)t + 1] = tpre[1][(size_t)t] + (n - nf);
+		for (int64_t k = nf; k < n; ++k) {
+			const int64_t x = localscan_swept_tile(k, d);
+			b.rag_most = std::max<int32_t>(b.rag_most, (int32_t)(localscan_tile_end(x, tile, ov, l2) - localscan_tile_start(x, tile, ov)));
+		}
+	}
+	b.tiles = tpre[0][(size_t)ntb] + tpre[1][(size_t)ntb];
+	return b;
 }
 
 }  // namespace at

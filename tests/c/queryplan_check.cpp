@@ -8,10 +8,13 @@
  *   2. the slice clamp at most = 0, 1 and 2^28, beyond it, and with a wanted size below 1;
  *   3. list keys round-trip at the extremes of rank and target, and their order is the ranking;
  *   4. the piece cutter never returns an empty piece, respects both caps except for a single oversized hit, covers every hit once;
- *   5. the prefix fit at capacity 0, at exactly one entry's end, and when everything fits.
+ *   5. the prefix fit at capacity 0, at exactly one entry's end, and when everything fits;
+ *   6. a block's tile prefix arrays, tile count and longest ragged tile against the loops of the local and the fit scan, at query
+ *      lengths 1 .. 1 024, tiles of 16, 64 and 1 024 columns, with and without a cutoff, over target lengths around every edge of the cut.
  * Exit status 0 and "queryplan_check: ok" when everything holds; every failure is printed.
  */
 #include "../../aligntools/c_amd/csrc/at_queryplan.h"
+#include "../../aligntools/c_amd/csrc/at_fitscan_plan.h"
 
 #include <climits>
 #include <cstdio>
@@ -223,6 +226,87 @@ static void check_fit()
 	}
 }
 
+/* the per-block loops of the local scan (every target, caller order) and of the fit scan (the block's targets) as they stood */
+struct RefTiles { std::vector<long long> tpre[2]; int64_t tiles; int32_t rag_most; };
+static RefTiles ref_tiles_local(const std::vector<int32_t> &t_len, int32_t tile, int64_t ov)
+{
+	const int64_t nt = (int64_t)t_len.size();
+	RefTiles r;
+	for (auto &v : r.tpre) v.assign((size_t)nt + 1, 0);
+	r.rag_most = 0;
+	for (int64_t t = 0; t < nt; ++t) {
+		const int64_t n = at::localscan_swept(t_len[(size_t)t], tile, ov), nf = at::localscan_swept_full(t_len[(size_t)t], tile, ov);
+		const int64_t d = at::localscan_dropped(t_len[(size_t)t], tile, ov);
+		r.tpre[0][(size_t)t + 1] = r.tpre[0][(size_t)t] + nf;
+		r.tpre[1][(size_t)t + 1] = r.tpre[1][(size_t)t] + (n - nf);
+		for (int64_t k2 = nf; k2 < n; ++k2) {
+			const int64_t x = at::localscan_swept_tile(k2, d);
+			r.rag_most = std::max<int32_t>(r.rag_most, (int32_t)(at::localscan_tile_end(x, tile, ov, t_len[(size_t)t]) - at::localscan_tile_start(x, tile, ov)));
+		}
+	}
+	r.tiles = r.tpre[0][(size_t)nt] + r.tpre[1][(size_t)nt];
+	return r;
+}
+static RefTiles ref_tiles_fit(const std::vector<int32_t> &tls, int64_t ta, int64_t ntb, int32_t l1, int32_t tile, int64_t ov)
+{
+	RefTiles r;
+	r.rag_most = 0;
+	for (auto &v : r.tpre) v.assign((size_t)ntb + 1, 0);
+	for (int64_t t = 0; t < ntb; ++t) {
+		const int32_t l2 = tls[(size_t)(ta + t)];
+		const int64_t n = at::fitscan_swept(l1, l2, tile, ov), nf = at::fitscan_swept_full(l1, l2, tile, ov);
+		const int64_t d = at::fitscan_dropped(l1, l2, tile, ov);
+		r.tpre[0][(size_t)t + 1] = r.tpre[0][(size_t)t] + nf;
+		r.tpre[1][(size_t)t + 1] = r.tpre[1][(size_t)t] + (n - nf);
+		for (int64_t k2 = nf; k2 < n; ++k2) {
+			const int64_t x = at::fitscan_swept_tile(k2, d);
+			r.rag_most = std::max<int32_t>(r.rag_most, (int32_t)(at::fitscan_tile_end(x, tile, ov, l2) - at::fitscan_tile_start(x, tile, ov)));
+		}
+	}
+	r.tiles = r.tpre[0][(size_t)ntb] + r.tpre[1][(size_t)ntb];
+	return r;
+}
+
+static void check_block_tiles()
+{
+	const int m = 2, u = -2, o = -5, e = -2;
+	long long blocks = 0, ragged = 0, full = 0, dropped = 0;
+	for (int32_t l1 : {1, 24, 37, 150, 1024})
+		for (int32_t T : {16, 64, 1024})
+			for (int fit = 0; fit < 2; ++fit)
+				for (int use_cutoff = 0; use_cutoff < 2; ++use_cutoff) {
+					const int32_t cutoff = m * l1 / 2;
+					const int64_t ov = fit ? at::fitscan_overlap(l1, use_cutoff, cutoff, m, u, o, e) : at::localscan_overlap(l1, use_cutoff, cutoff, m, u, o, e);
+					/* around every edge: empty, one short of the query, the query, one tile, the full shape and its neighbours, whole tiles, one past */
+					std::vector<int32_t> t_len;
+					for (int64_t l2 : {(int64_t)0, (int64_t)l1 - 1, (int64_t)l1, (int64_t)T, T + ov - 1, T + ov, T + ov + 1, 5 * (int64_t)T, 5 * (int64_t)T + 1, 3 * (int64_t)T + ov,
+					                   3 * (int64_t)T + ov + 1})
+						t_len.push_back((int32_t)l2);
+					std::vector<long long> tpre[2];
+					tpre[0].assign(3, 77);       /* (what an earlier block left is overwritten) */
+					auto same = [&](const at::BlockTiles &b, const RefTiles &r, const char *what) {
+						CHECK(tpre[0] == r.tpre[0] && tpre[1] == r.tpre[1] && b.tiles == r.tiles && b.rag_most == r.rag_most,
+						      "%s: l1=%d tile=%d ov=%lld cutoff=%d: %lld tiles, longest ragged %d; the loop has %lld and %d", what, l1, T, (long long)ov, use_cutoff,
+						      (long long)b.tiles, b.rag_most, (long long)r.tiles, r.rag_most);
+						++blocks; ragged += r.tpre[1].back() > 0; full += r.tpre[0].back() > 0;
+					};
+					if (!fit) {
+						same(at::block_tiles(t_len.data(), (int64_t)t_len.size(), T, ov, tpre), ref_tiles_local(t_len, T, ov), "local");
+						for (int32_t l2 : t_len) dropped += at::localscan_dropped(l2, T, ov) > 0;
+						continue;
+					}
+					/* fit: the targets by length, the block those no shorter than the query (the shorter ones never reach the function) */
+					std::vector<int32_t> tls = t_len;
+					std::stable_sort(tls.begin(), tls.end());
+					const int64_t nt = (int64_t)tls.size(), ta = std::lower_bound(tls.begin(), tls.end(), l1) - tls.begin();
+					same(at::block_tiles(tls.data() + ta, nt - ta, T, ov, tpre), ref_tiles_fit(tls, ta, nt - ta, l1, T, ov), "fit block");
+					same(at::block_tiles(tls.data(), 0, T, ov, tpre), ref_tiles_fit(tls, 0, 0, l1, T, ov), "no targets");
+				}
+	/* (the cases do reach the paths they are chosen for) */
+	CHECK(blocks == 5 * 3 * (2 + 2 * 2) && ragged > 0 && full > 0 && dropped > 0, "%lld blocks, %lld with ragged tiles, %lld with full ones, %lld targets with dropped tiles", blocks,
+	      ragged, full, dropped);
+}
+
 int main()
 {
 	for (int strands = 1; strands <= 3; ++strands) {
@@ -233,6 +317,7 @@ int main()
 	check_keys();
 	check_pieces();
 	check_fit();
+	check_block_tiles();
 	if (g_failures) { printf("queryplan_check: %d failures\n", g_failures); return 1; }
 	printf("queryplan_check: ok\n");
 	return 0;

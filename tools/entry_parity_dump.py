@@ -3,6 +3,10 @@ per call, to compare two builds of the library byte by byte (`AT_LIB_PATH=... en
 
     search in five modes, scan, scan_local and scan_hits on 6 queries of two lengths against 3 targets of 40, 173 and 400 bases,
     both strands; allpairs_hits in four modes on the 9 sequences; scans and allpairs_hits with CIGARs;
+    the tiled scans (scan_local, scan_fit) once more where their tiles, blocks and windows differ: scan_fit with a fourth target of
+    30 bases (shorter than the 37-base queries: the block filter and the length sort); both at tile_cols 16 and 64 (dropped tiles, a
+    full and a ragged pass on the long targets, ragged-only short ones); both with min_score at half the perfect score of the 24-base
+    queries; both with an N in one target (byte words) at tile_cols 16;
     all of it with AT_ALLPAIRS_CHUNK=7 (many slices) and unset
 
 The millisecond figures in at_last_config (`sweep=`, `select=`) are blanked.  Seconds."""
@@ -30,6 +34,9 @@ for q in range(6):
     at = rng.randint(0, len(t) - n)
     s = "".join(rng.choice("ACGT") if rng.random() < 0.06 else c for c in t[at:at + n])
     queries.append(A.revcomp(s).decode() if q % 3 == 2 else s)
+rng4 = random.Random(2121)
+targets4 = targets + ["".join(rng4.choice("ACGT") for _ in range(30))]
+targets_n = [targets[0], targets[1][:90] + "N" + targets[1][91:], targets[2], targets4[3]]
 
 
 def plain(v):
@@ -68,4 +75,14 @@ for chunk in ("7", None):
     for mode, threshold in (("overlap", 12), ("local", 30), ("global", -60), ("edit", 30)):
         al.set_scoring(*(UNIT if mode == "edit" else AFFINE))
         emit(tag + "allpairs_hits " + mode, al.allpairs_hits(mode, reads, threshold, cigar=mode != "edit"), al.last_config)
+    al.set_scoring(*AFFINE)
+    emit(tag + "scan_fit 4 targets", al.scan_fit(queries, targets4, k=2, strands="both", cigar=True), al.last_config)
+    for tile in (16, 64):
+        emit(tag + "scan_local tile=%d" % tile, al.scan_local(queries, targets4, k=2, strands="both", cigar=True, tile_cols=tile), al.last_config)
+        emit(tag + "scan_fit tile=%d" % tile, al.scan_fit(queries, targets4, k=2, strands="both", cigar=True, tile_cols=tile), al.last_config)
+    half = AFFINE[0] * 24 // 2
+    emit(tag + "scan_local min_score", al.scan_local(queries, targets4, k=2, min_score=half, strands="both", cigar=True), al.last_config)
+    emit(tag + "scan_fit min_score", al.scan_fit(queries, targets4, k=2, min_score=half, strands="both", cigar=True), al.last_config)
+    emit(tag + "scan_local N", al.scan_local(queries, targets_n, k=2, strands="both", cigar=True, tile_cols=16), al.last_config)
+    emit(tag + "scan_fit N", al.scan_fit(queries, targets_n, k=2, strands="both", cigar=True, tile_cols=16), al.last_config)
 al.close()
